@@ -4,7 +4,7 @@ timeout 400 python -m pytest tests/ -m gpu -q 2>&1 | tail -2
 echo "=== block bench after reduce fix ==="
 timeout 250 python bench.py --mode block --block-batch 16 --steps 8 --warmup 2 --skip-cpu-baseline 2>&1 | tail -1
 echo "=== adversarial verify 10pct invalid ==="
-timeout 200 python bench.py --tuples 262144 --invalid-permille 100 --steps 6 --warmup 2 --skip-cpu-baseline 2>&1 | tail -1
+timeout 200 python bench.py --full --mode verify --tuples 262144 --invalid-permille 100 --steps 6 --warmup 2 --skip-cpu-baseline 2>&1 | tail -1
 echo "=== ecdsa staged ==="
 timeout 200 python - <<'PYEOF'
 import ctypes
