@@ -239,17 +239,20 @@ __device__ __forceinline__ void fe26_mul_inner(u64 t[19], const fe26 &a,
 
 __device__ __forceinline__ void fe26_sqr_inner(u64 t[19], const fe26 &a) {
   KV26_CHECK_MUL_IN(a);
+  /* cross terms use the DOUBLED operand limb (<= 2^30 doubles to <= 2^31, still
+   * u32) instead of shifting the 19 u64 column sums; the column values are
+   * identical, so the < 2^64 bound is the one stated above */
+  u32 d[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) d[i] = a.l[i] << 1;
 #pragma unroll
   for (int k = 0; k < 19; k++) t[k] = 0;
 #pragma unroll
   for (int i = 0; i < 10; i++) {
+    t[2 * i] += (u64)a.l[i] * a.l[i];
 #pragma unroll
-    for (int j = i + 1; j < 10; j++) t[i + j] += (u64)a.l[i] * a.l[j];
+    for (int j = i + 1; j < 10; j++) t[i + j] += (u64)d[i] * a.l[j];
   }
-#pragma unroll
-  for (int k = 0; k < 19; k++) t[k] <<= 1;
-#pragma unroll
-  for (int i = 0; i < 10; i++) t[2 * i] += (u64)a.l[i] * a.l[i];
 }
 
 __device__ __forceinline__ void fe26_mul(fe26 &r, const fe26 &a, const fe26 &b) {
@@ -368,6 +371,46 @@ __device__ __forceinline__ int fe26_eq(const fe26 &a, const fe26 &b) {
 #pragma unroll
   for (int i = 0; i < 10; i++) d |= ta.l[i] ^ tb.l[i];
   return d == 0;
+}
+
+/* "is a == 0 (mod p)?" without computing the canonical value. Valid for every
+ * limb < 2^31 (any magnitude <= 15 under the negate convention
+ * limb <= 2m*2^26; the group ops feed it z <= 2 and h, rr <= 5).
+ *   1. one carry sweep: limbs < 2^26, carry c <= 32 = value >> 260
+ *   2. fold c (2^260 == R0 + 2^36) and the top limb's bits 22.. (2^256 ==
+ *      2^32 + 977) into l0/l1: value V < 2^256 + 2^43 < 2p, so V == 0 (mod p)
+ *      iff V is 0 or p; l2..l8 < 2^26, l9 < 2^22, l0 < 2^27, l1 < 2^26 + 2^16
+ *   3. carry l0 -> l1 -> c1 (c1 <= 1) and add c1 into l2 WITHOUT masking it:
+ *      V == 0 iff every limb (and c1) is 0. V == p iff the limbs are p's
+ *      digits with l2 + c1 == 2^26-1: a carry out of l2 would need
+ *      l2 + c1 == 2^27-1 to leave p's digit behind, which c1 <= 1 cannot give. */
+__device__ __forceinline__ int fe26_normalizes_to_zero(const fe26 &a) {
+#ifdef KV_HOST_TEST
+  for (int _i = 0; _i < 10; _i++) assert(a.l[_i] < (1u << 31));
+#endif
+  u32 l[10];
+  u32 c = 0;
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    u32 d = a.l[i] + c;
+    l[i] = d & KV26_M;
+    c = d >> 26;
+  }
+  u32 x = l[9] >> 22;
+  l[9] &= 0x3FFFFF;
+  l[0] += c * (u32)KV26_R0 + x * 977u;
+  l[1] += (c << 10) + (x << 6) + (l[0] >> 26);
+  l[0] &= KV26_M;
+  l[2] += l[1] >> 26;
+  l[1] &= KV26_M;
+  u32 z0 = l[0] | l[1] | l[2] | l[9];
+  u32 z1 = (l[0] ^ 0x3D0u) & (l[1] ^ 0x40u) & l[2] & (l[9] ^ 0x3C00000u);
+#pragma unroll
+  for (int i = 3; i < 9; i++) {
+    z0 |= l[i];
+    z1 &= l[i];
+  }
+  return (z0 == 0) | (z1 == KV26_M);
 }
 
 /* conversions at the byte/u64 boundary */
@@ -686,29 +729,25 @@ __device__ __forceinline__ void gej_set_infinity(gej &r) {
 }
 
 __device__ __forceinline__ int gej_is_infinity(const gej &a) {
-  return fe26_is_zero(a.z);
+  return fe26_normalizes_to_zero(a.z); /* z magnitude <= 2 */
 }
 
 /* doubling: straight-line, valid for z==0 (result keeps z==0).
  * y == 0 cannot occur on secp256k1 (no 2-torsion). Inputs magnitude <= 2. */
 __device__ __forceinline__ void gej_double_impl(gej &r, const gej &a) {
-  fe26 A, B, C, D, E, F, t, zz;
+  /* The small factors ride on a mul operand (4x, 2y: magnitude <= 8) instead
+   * of on the product, so D = 4*x*y^2 and nz = 2*y*z come out of the multiply
+   * at magnitude <= 2 and need no carry sweep of their own. */
+  fe26 A, B, C, D, E, F, t, x4, y2;
   fe26_sqr(A, a.x);        /* 1 */
   fe26_sqr(B, a.y);        /* 1 */
   fe26_sqr(C, B);          /* 1 */
-  fe26_mul(zz, a.y, a.z);  /* 1 */
-  fe26_add(t, a.x, B);     /* 2+2=4 */
-  fe26_sqr(t, t);          /* 1 */
+  x4 = a.x;
+  fe26_mul_int(x4, 4);     /* 8 */
+  fe26_mul(D, x4, B);      /* 1 */
   E = A;
   fe26_mul_int(E, 3);      /* 6 */
   fe26_sqr(F, E);          /* 1 */
-  fe26 nA, nC;
-  fe26_neg(nA, A, 2);      /* 3 */
-  fe26_neg(nC, C, 2);      /* 3 */
-  fe26_add(t, t, nA);
-  fe26_add(D, t, nC);      /* 1+3+3 = 8 (pre-double) */
-  fe26_add(D, D, D);       /* 16 */
-  fe26_norm_weak(D);       /* -> 2 */
   fe26 nx, ny, nz, nD;
   fe26_neg(nD, D, 2);      /* 3 */
   fe26_add(nx, F, nD);
@@ -725,8 +764,8 @@ __device__ __forceinline__ void gej_double_impl(gej &r, const gej &a) {
   fe26_neg(nC8, C8, 16);   /* 17 */
   fe26_add(ny, t, nC8);    /* 19 <= 31 */
   fe26_norm_weak(ny);      /* -> 2 */
-  fe26_add(nz, zz, zz);    /* 4 */
-  fe26_norm_weak(nz);      /* -> 2 */
+  fe26_add(y2, a.y, a.y);  /* 4 */
+  fe26_mul(nz, y2, a.z);   /* 1 */
   r.x = nx;
   r.y = ny;
   r.z = nz;
@@ -753,9 +792,14 @@ __device__ __forceinline__ void gej_cmov(gej &r, const gej &a, u64 cond) {
   fe26_cmov(r.z, a.z, c);
 }
 
-/* mixed add (b affine, magnitude <= 3 after phi/negation); a coords mag <= 2 */
-__device__ __forceinline__ void gej_add_ge_impl(gej &r, const gej &a, const ge &b) {
-  u64 a_inf = (u64)fe26_is_zero(a.z);
+/* mixed add (b affine, magnitude <= 3 after phi/negation); a coords mag <= 2.
+ * With ZR the z ratio is exported too: r.z == a.z * zr (zr magnitude <= 2).
+ * The regular path has nz = 2*z1*h, so zr = 2h; the equal-x doubling path has
+ * nz = 2*y1*z1, so zr = 2*y1. Meaningless when a or r is infinity. */
+template <bool ZR>
+__device__ __forceinline__ void gej_add_ge_core(gej &r, fe26 &zr, const gej &a,
+                                                const ge &b) {
+  u64 a_inf = (u64)fe26_normalizes_to_zero(a.z); /* z <= 2 */
   fe26 z1z1, u2, s2, h, hh, i, j, rr, v, t;
   fe26_sqr(z1z1, a.z);       /* 1 */
   fe26_mul(s2, b.y, a.z);    /* 1 */
@@ -766,9 +810,11 @@ __device__ __forceinline__ void gej_add_ge_impl(gej &r, const gej &a, const ge &
   fe26_neg(nY, a.y, 2);      /* 3 */
   fe26_add(h, u2, nX);       /* 5 */
   fe26_add(rr, s2, nY);      /* 5 */
-  if (!a_inf && fe26_is_zero(h)) {
-    /* rare: same x. rr==0 -> doubling; else opposite points -> infinity */
-    if (fe26_is_zero(rr)) {
+  if (!a_inf && fe26_normalizes_to_zero(h)) { /* h <= 5 */
+    /* rare: same x. rr==0 -> doubling; else opposite points -> infinity.
+     * (Moving this into one cold __noinline__ function shrinks the pair-window
+     * frame from 47k to 36k instructions and measured no faster.) */
+    if (fe26_normalizes_to_zero(rr)) {        /* rr <= 5 */
       gej t2;
       gej ain = a;
       fe26_norm_weak(ain.x);
@@ -776,10 +822,19 @@ __device__ __forceinline__ void gej_add_ge_impl(gej &r, const gej &a, const ge &
       fe26_norm_weak(ain.z);
       gej_double_impl(t2, ain);
       r = t2;
+      if (ZR) {
+        fe26_add(zr, ain.y, ain.y); /* 4 */
+        fe26_norm_weak(zr);         /* -> 2 */
+      }
     } else {
       gej_set_infinity(r);
+      if (ZR) fe26_set_int(zr, 0);
     }
     return;
+  }
+  if (ZR) {
+    fe26_add(zr, h, h);      /* 10 */
+    fe26_norm_weak(zr);      /* -> 2 */
   }
   fe26 zz;
   fe26_add(zz, a.z, h);      /* 7 */
@@ -829,13 +884,24 @@ __device__ __forceinline__ void gej_add_ge_impl(gej &r, const gej &a, const ge &
   r.z = nz;
 }
 
+__device__ __forceinline__ void gej_add_ge_impl(gej &r, const gej &a, const ge &b) {
+  fe26 unused;
+  gej_add_ge_core<false>(r, unused, a, b);
+}
+
 /* full add; a and b coords magnitude <= 3 */
 __device__ KV_GROUP_ATTR void gej_add_ge(gej &r, const gej &a, const ge &b) {
   gej_add_ge_impl(r, a, b);
 }
 
+/* mixed add that also returns zr = r.z / a.z (table chains) */
+__device__ KV_GROUP_ATTR void gej_add_ge_zr(gej &r, fe26 &zr, const gej &a,
+                                            const ge &b) {
+  gej_add_ge_core<true>(r, zr, a, b);
+}
+
 __device__ KV_GROUP_ATTR void gej_add(gej &r, const gej &a, const gej &b) {
-  u64 a_inf = (u64)fe26_is_zero(a.z);
+  u64 a_inf = (u64)fe26_normalizes_to_zero(a.z); /* z <= 3 */
   fe26 z1z1, z2z2, u1, u2, s1, s2, h, i, j, rr, v, t;
   fe26_sqr(z1z1, a.z);      /* 1 */
   fe26_sqr(z2z2, b.z);      /* 1 */
@@ -850,8 +916,8 @@ __device__ KV_GROUP_ATTR void gej_add(gej &r, const gej &a, const gej &b) {
   fe26_neg(ns1, s1, 2);     /* 3 */
   fe26_add(h, u2, nu1);     /* 5 */
   fe26_add(rr, s2, ns1);    /* 5 */
-  if (!a_inf && !fe26_is_zero(b.z) && fe26_is_zero(h)) {
-    if (fe26_is_zero(rr)) {
+  if (!a_inf && !fe26_normalizes_to_zero(b.z) && fe26_normalizes_to_zero(h)) {
+    if (fe26_normalizes_to_zero(rr)) { /* h, rr <= 5 */
       gej t2;
       gej ain = a;
       fe26_norm_weak(ain.x);

@@ -300,6 +300,99 @@ __device__ __forceinline__ void glv_recode_signed(const glv_half &h,
 }
 #endif
 
+/* Signed windows need 1P..8P, unsigned ones 1P..15P. */
+#ifdef KV_SIGNED_PTAB
+#define KV_PTAB_MAX 8
+#else
+#define KV_PTAB_MAX 15
+#endif
+
+/* Per-verify ladder constants, handed to the window frames by one reference.
+ * The ladder runs on the curve y² = x³ + 7·Zg⁶ ("effective affine"), where the
+ * per-lane P table needs no inversion; (x, y) on secp256k1 maps to
+ * (x·Zg², y·Zg³) there. */
+struct ladder_consts {
+  fe26 beta; /* GLV β */
+  fe26 zg2;  /* Zg² */
+  fe26 zg3;  /* Zg³ */
+  fe26 bzg2; /* β·Zg² */
+};
+
+/* Per-lane P table without an inversion. The chain acc_k = acc_{k-1} + P has
+ * Z_k = Z_{k-1}·zr_k, so with Zg = Z_max and m_k = ∏_{j>k} zr_j = Zg/Z_k the
+ * pair (X_k·m_k², Y_k·m_k³) is k·P over the COMMON denominator Zg: affine on
+ * the isomorphic curve above. 5 field ops per entry instead of one Fermat
+ * inversion plus back-substitution; the caller pays Zg back into the result's
+ * z. Entries are mul outputs (magnitude <= 2). zg is Zg, magnitude <= 2. */
+__device__ inline void ecmult_ptab_build(ge *ptab, ladder_consts &lc, fe26 &zg,
+                                         const ge &P) {
+  fe26 zr[KV_PTAB_MAX + 1];
+  gej acc;
+  acc.x = P.x;
+  acc.y = P.y;
+  fe26_set_int(acc.z, 1);
+#pragma unroll 1
+  for (int k = 2; k <= KV_PTAB_MAX; k++) {
+    gej t;
+    gej_add_ge_zr(t, zr[k], acc, P); /* k == 2 is the equal-x doubling path */
+    acc = t;
+    ptab[k].x = acc.x;
+    ptab[k].y = acc.y;
+  }
+  zg = acc.z;
+  fe26 m = zr[KV_PTAB_MAX]; /* m_{max-1} */
+#pragma unroll 1
+  for (int k = KV_PTAB_MAX - 1; k >= 2; k--) {
+    fe26 m2, m3;
+    fe26_sqr(m2, m);
+    fe26_mul(m3, m2, m);
+    fe26_mul(ptab[k].x, ptab[k].x, m2);
+    fe26_mul(ptab[k].y, ptab[k].y, m3);
+    if (k > 2) fe26_mul(m, m, zr[k]);
+  }
+  /* entry 1 is P itself: m_1 = Zg */
+  fe26_sqr(lc.zg2, zg);
+  fe26_mul(lc.zg3, lc.zg2, zg);
+  fe26_mul(ptab[1].x, P.x, lc.zg2);
+  fe26_mul(ptab[1].y, P.y, lc.zg3);
+  ptab[0] = ptab[1]; /* digit 0: add computed then discarded by cmov — a
+                        well-formed point keeps magnitudes in range */
+}
+
+/* table entry -> the point a ladder stream adds: G entries are mapped onto the
+ * ladder's curve first (P entries already live there), then φ (β·x) and the
+ * stream's sign are applied */
+template <bool IS_G, bool PHI>
+__device__ __forceinline__ void ladder_entry(ge &e, const ge &tab,
+                                             const ladder_consts &lc, u64 neg) {
+  e = tab;
+  if (IS_G) { /* one multiply per coordinate: φ's β rides on Zg² */
+    fe26 mx, my;
+    fe26_mul(mx, e.x, PHI ? lc.bzg2 : lc.zg2);
+    fe26_mul(my, e.y, lc.zg3);
+    e.x = mx;
+    e.y = my;
+  } else if (PHI) {
+    fe26 bx;
+    fe26_mul(bx, e.x, lc.beta);
+    e.x = bx;
+  }
+  fe26 ny;
+  fe26_neg(ny, e.y, 2);
+  fe26_cmov(e.y, ny, (u32)neg);
+}
+
+template <bool IS_G, bool PHI>
+__device__ __forceinline__ void ladder_add(gej &R, const ge &tab,
+                                           const ladder_consts &lc, u64 digit,
+                                           u64 neg) {
+  ge e;
+  gej t;
+  ladder_entry<IS_G, PHI>(e, tab, lc, neg);
+  gej_add_ge_impl(t, R, e);
+  gej_cmov(R, t, (u64)(digit != 0));
+}
+
 /* One full ladder window in ONE call frame: 4 doublings + the 4 stream adds
  * (G, φG, P, φP). The group ops inline INSIDE this body, so the accumulator
  * crosses the noinline ABI once per window instead of five times — the r02
@@ -307,60 +400,47 @@ __device__ __forceinline__ void glv_recode_signed(const glv_half &h,
  * dominant memory traffic (~119KB/verify). Full kernel-wide inlining is not
  * an option: it reproducibly hangs gfx950 (measured again this round); this
  * bounded body (~5k instructions) stays under that cliff. */
+template <bool DOUBLE>
+__device__ __forceinline__ void gej_window_impl(gej &R, const ge *ptab,
+                                                const ladder_consts &lc,
+                                                u64 g_active, u64 dg1, u64 ng1,
+                                                u64 dg2, u64 ng2, u64 dp1,
+                                                u64 np1, u64 dp2, u64 np2) {
+  if (DOUBLE) {
+    gej t;
+    gej_double_impl(t, R);
+    gej_double_impl(R, t);
+    gej_double_impl(t, R);
+    gej_double_impl(R, t);
+  }
+  if (g_active) { /* wave-uniform: G adds land on every second window */
+    ladder_add<true, false>(R, KV_G_TABLE8[dg1], lc, dg1, ng1); /* G (8-bit) */
+    ladder_add<true, true>(R, KV_G_TABLE8[dg2], lc, dg2, ng2);  /* φG */
+  }
+  ladder_add<false, false>(R, ptab[dp1], lc, dp1, np1); /* P */
+  ladder_add<false, true>(R, ptab[dp2], lc, dp2, np2);  /* φP */
+}
+
 __device__ KV_GROUP_ATTR void gej_window_step(gej &R, const ge *ptab,
-                                              const fe26 &beta, u64 g_active,
-                                              u64 dg1, u64 ng1,
+                                              const ladder_consts &lc,
+                                              u64 g_active, u64 dg1, u64 ng1,
                                               u64 dg2, u64 ng2, u64 dp1, u64 np1,
                                               u64 dp2, u64 np2) {
-  gej t;
-  gej_double_impl(t, R);
-  gej_double_impl(R, t);
-  gej_double_impl(t, R);
-  gej_double_impl(R, t);
-  if (g_active) { /* wave-uniform: G adds land on every second window */
-  /* G stream (8-bit fixed-base digits) */
-  {
-    ge e = KV_G_TABLE8[dg1];
-    fe26 ny;
-    fe26_neg(ny, e.y, 2);
-    fe26_cmov(e.y, ny, (u32)ng1);
-    gej_add_ge_impl(t, R, e);
-    gej_cmov(R, t, (u64)(dg1 != 0));
-  }
-  /* φG stream: (β·x, ±y) */
-  {
-    ge e = KV_G_TABLE8[dg2];
-    fe26 bx;
-    fe26_mul(bx, e.x, beta);
-    e.x = bx;
-    fe26 ny;
-    fe26_neg(ny, e.y, 2);
-    fe26_cmov(e.y, ny, (u32)ng2);
-    gej_add_ge_impl(t, R, e);
-    gej_cmov(R, t, (u64)(dg2 != 0));
-  }
-  } /* g_active */
-  /* P stream (mixed add vs the affine per-lane table) */
-  {
-    ge e = ptab[dp1];
-    fe26 ny;
-    fe26_neg(ny, e.y, 2);
-    fe26_cmov(e.y, ny, (u32)np1);
-    gej_add_ge_impl(t, R, e);
-    gej_cmov(R, t, (u64)(dp1 != 0));
-  }
-  /* φP stream: (β·x, ±y) */
-  {
-    ge e = ptab[dp2];
-    fe26 bx;
-    fe26_mul(bx, e.x, beta);
-    e.x = bx;
-    fe26 ny;
-    fe26_neg(ny, e.y, 2);
-    fe26_cmov(e.y, ny, (u32)np2);
-    gej_add_ge_impl(t, R, e);
-    gej_cmov(R, t, (u64)(dp2 != 0));
-  }
+  gej_window_impl<true>(R, ptab, lc, g_active, dg1, ng1, dg2, ng2, dp1, np1,
+                        dp2, np2);
+}
+
+/* The ladder's top window: R starts at infinity, so its four doublings would
+ * double infinity. This frame sets R and runs the window's adds only (all
+ * digits zero leaves R at infinity). */
+__device__ KV_GROUP_ATTR void gej_window_first(gej &R, const ge *ptab,
+                                               const ladder_consts &lc, u64 dg1,
+                                               u64 ng1, u64 dg2, u64 ng2,
+                                               u64 dp1, u64 np1, u64 dp2,
+                                               u64 np2) {
+  gej_set_infinity(R);
+  gej_window_impl<false>(R, ptab, lc, 1, dg1, ng1, dg2, ng2, dp1, np1, dp2,
+                         np2);
 }
 
 /* Pair-window frames are the DEFAULT (measured 41.1M vs 39.6M verifies/s);
@@ -375,174 +455,66 @@ __device__ KV_GROUP_ATTR void gej_window_step(gej &R, const ge *ptab,
  * accumulator's ABI crossings (17 frames vs 33) at the cost of a ~2x body —
  * under the gfx950 long-body hang cliff (full inlining still hangs). */
 __device__ __forceinline__ void gej_window_pair_impl(
-    gej &R, const ge *ptab, const fe26 &beta, u64 dg1, u64 ng1, u64 dg2, u64 ng2,
-    u64 hp1, u64 hn1, u64 hp2, u64 hn2, /* odd-window P digits + negs */
+    gej &R, const ge *ptab, const ladder_consts &lc, u64 dg1, u64 ng1, u64 dg2,
+    u64 ng2, u64 hp1, u64 hn1, u64 hp2, u64 hn2, /* odd-window P digits + negs */
     u64 lp1, u64 ln1, u64 lp2, u64 ln2 /* even-window P digits + negs */) {
-  gej t;
-  gej_double_impl(t, R);
-  gej_double_impl(R, t);
-  gej_double_impl(t, R);
-  gej_double_impl(R, t);
-  { /* odd window: P streams only */
-    ge e = ptab[hp1];
-    fe26 ny;
-    fe26_neg(ny, e.y, 2);
-    fe26_cmov(e.y, ny, (u32)hn1);
-    gej_add_ge_impl(t, R, e);
-    gej_cmov(R, t, (u64)(hp1 != 0));
-  }
-  {
-    ge e = ptab[hp2];
-    fe26 bx;
-    fe26_mul(bx, e.x, beta);
-    e.x = bx;
-    fe26 ny;
-    fe26_neg(ny, e.y, 2);
-    fe26_cmov(e.y, ny, (u32)hn2);
-    gej_add_ge_impl(t, R, e);
-    gej_cmov(R, t, (u64)(hp2 != 0));
-  }
-  gej_double_impl(t, R);
-  gej_double_impl(R, t);
-  gej_double_impl(t, R);
-  gej_double_impl(R, t);
-  { /* even window: G comb + P streams */
-    ge e = KV_G_TABLE8[dg1];
-    fe26 ny;
-    fe26_neg(ny, e.y, 2);
-    fe26_cmov(e.y, ny, (u32)ng1);
-    gej_add_ge_impl(t, R, e);
-    gej_cmov(R, t, (u64)(dg1 != 0));
-  }
-  {
-    ge e = KV_G_TABLE8[dg2];
-    fe26 bx;
-    fe26_mul(bx, e.x, beta);
-    e.x = bx;
-    fe26 ny;
-    fe26_neg(ny, e.y, 2);
-    fe26_cmov(e.y, ny, (u32)ng2);
-    gej_add_ge_impl(t, R, e);
-    gej_cmov(R, t, (u64)(dg2 != 0));
-  }
-  {
-    ge e = ptab[lp1];
-    fe26 ny;
-    fe26_neg(ny, e.y, 2);
-    fe26_cmov(e.y, ny, (u32)ln1);
-    gej_add_ge_impl(t, R, e);
-    gej_cmov(R, t, (u64)(lp1 != 0));
-  }
-  {
-    ge e = ptab[lp2];
-    fe26 bx;
-    fe26_mul(bx, e.x, beta);
-    e.x = bx;
-    fe26 ny;
-    fe26_neg(ny, e.y, 2);
-    fe26_cmov(e.y, ny, (u32)ln2);
-    gej_add_ge_impl(t, R, e);
-    gej_cmov(R, t, (u64)(lp2 != 0));
-  }
+  /* odd window: P streams only */
+  gej_window_impl<true>(R, ptab, lc, 0, 0, 0, 0, 0, hp1, hn1, hp2, hn2);
+  /* even window: G comb + P streams */
+  gej_window_impl<true>(R, ptab, lc, 1, dg1, ng1, dg2, ng2, lp1, ln1, lp2, ln2);
 }
 
 __device__ KV_GROUP_ATTR void gej_window_step2(gej &R, const ge *ptab,
-                                               const fe26 &beta, u64 dg1, u64 ng1,
-                                               u64 dg2, u64 ng2, u64 hp1, u64 hn1,
-                                               u64 hp2, u64 hn2, u64 lp1, u64 ln1,
+                                               const ladder_consts &lc, u64 dg1,
+                                               u64 ng1, u64 dg2, u64 ng2,
+                                               u64 hp1, u64 hn1, u64 hp2,
+                                               u64 hn2, u64 lp1, u64 ln1,
                                                u64 lp2, u64 ln2) {
-  gej_window_pair_impl(R, ptab, beta, dg1, ng1, dg2, ng2, hp1, hn1, hp2, hn2,
+  gej_window_pair_impl(R, ptab, lc, dg1, ng1, dg2, ng2, hp1, hn1, hp2, hn2,
                        lp1, ln1, lp2, ln2);
 }
 
 #ifdef KV_QUAD_WINDOWS
 /* four windows (two pairs) per frame: 9 frames per ladder */
 __device__ KV_GROUP_ATTR void gej_window_step4(gej &R, const ge *ptab,
-                                               const fe26 &beta,
+                                               const ladder_consts &lc,
                                                const u64 a[12], const u64 b[12]) {
-  gej_window_pair_impl(R, ptab, beta, a[0], a[1], a[2], a[3], a[4], a[5], a[6],
+  gej_window_pair_impl(R, ptab, lc, a[0], a[1], a[2], a[3], a[4], a[5], a[6],
                        a[7], a[8], a[9], a[10], a[11]);
-  gej_window_pair_impl(R, ptab, beta, b[0], b[1], b[2], b[3], b[4], b[5], b[6],
+  gej_window_pair_impl(R, ptab, lc, b[0], b[1], b[2], b[3], b[4], b[5], b[6],
                        b[7], b[8], b[9], b[10], b[11]);
 }
 #endif
 #endif
 
-/* R = gs·G + ps·P via GLV-split 4-bit windows: 33 window steps of 4 doublings
- * + 4 selected adds (G, φG, P, φP streams; φ applied at add time as one β·x
+/* R = gs·G + ps·P via GLV-split 4-bit windows: 33 window steps (the top one
+ * without doublings, R being infinity there) of 4 doublings + 4 selected adds (G, φG, P, φP streams; φ applied at add time as one β·x
  * field multiply; negative half-scalars negate the added point's y). */
 __device__ inline void ecmult_double(gej &R, const sc &gs, const sc &ps,
                                      const ge &P) {
   glv_half g1h, g2h, p1h, p2h;
   glv_split(gs, g1h, g2h);
   glv_split(ps, p1h, p2h);
-  /* Per-lane P table in AFFINE form, batch-inverted with Montgomery's trick.
-   * The round-1 Jacobian table kept ~252MB of in-flight per-lane tables
-   * (16 entries x 120B x 131k resident lanes) — right at the 256MB MALL
-   * capacity — and its dynamic-indexed scratch loads paid ~44KB of fetch
-   * per verify (r01 PMC). Affine entries are 80B (working set ~168MB, fits
-   * MALL), and the P streams become MIXED adds (11 vs 16 fe_muls); the one
-   * extra field inversion (+~360 fe_muls with the back-substitution) is
-   * paid back by the 66 cheaper ladder adds (-330). */
-#ifdef KV_SIGNED_PTAB
-#define KV_PTAB_MAX 8
-#else
-#define KV_PTAB_MAX 15
-#endif
+  /* Per-lane P table, affine over the common denominator Zg (80B entries:
+   * the working set fits MALL and the P streams are MIXED adds, 11 vs 16
+   * fe_muls). The ladder runs on the isomorphic curve where these entries
+   * are affine; Zg is paid back into R.z below. */
   ge ptab[KV_PTAB_MAX + 1];
-  {
-    fe26 ztab[KV_PTAB_MAX + 1], pref[KV_PTAB_MAX + 1];
-    gej acc;
-    acc.x = P.x;
-    acc.y = P.y;
-    fe26_set_int(acc.z, 1);
-    ptab[1] = P;
-#pragma unroll 1
-    for (int k = 2; k <= KV_PTAB_MAX; k++) {
-      gej t;
-      gej_add_ge(t, acc, P);
-      acc = t;
-      ptab[k].x = acc.x;
-      ptab[k].y = acc.y;
-      ztab[k] = acc.z;
-    }
-    /* batch-invert z2..zmax: one fe26_inv + 3 muls per entry */
-    pref[2] = ztab[2];
-#pragma unroll 1
-    for (int k = 3; k <= KV_PTAB_MAX; k++) fe26_mul(pref[k], pref[k - 1], ztab[k]);
-    fe26 inv;
-    fe26_inv(inv, pref[KV_PTAB_MAX]);
-#pragma unroll 1
-    for (int k = KV_PTAB_MAX; k >= 2; k--) {
-      fe26 zi;
-      if (k > 2) {
-        fe26_mul(zi, inv, pref[k - 1]);
-        fe26_mul(inv, inv, ztab[k]);
-      } else {
-        zi = inv;
-      }
-      fe26 zi2, zi3;
-      fe26_sqr(zi2, zi);
-      fe26_mul(zi3, zi2, zi);
-      fe26_mul(ptab[k].x, ptab[k].x, zi2);
-      fe26_mul(ptab[k].y, ptab[k].y, zi3);
-    }
-    ptab[0] = ptab[1]; /* digit 0: add computed then discarded by cmov — a
-                          well-formed point keeps magnitudes in range */
-  }
+  ladder_consts lc;
+  fe26 zg;
+  ecmult_ptab_build(ptab, lc, zg, P);
 #ifdef KV_SIGNED_PTAB
   int8_t dp1[33], dp2[33];
   glv_recode_signed(p1h, dp1);
   glv_recode_signed(p2h, dp2);
 #endif
-  fe26 beta;
   {
     fe bu;
 #pragma unroll
     for (int i = 0; i < 4; i++) bu.n[i] = GLV_BETA[i];
-    fe26_from_fe(beta, bu);
+    fe26_from_fe(lc.beta, bu);
+    fe26_mul(lc.bzg2, lc.beta, lc.zg2);
   }
-  gej_set_infinity(R);
   /* per-stream digit/neg accessors: unsigned fixed windows by default,
    * signed fixed windows (8-entry table) under KV_SIGNED_PTAB */
 #ifdef KV_SIGNED_PTAB
@@ -556,11 +528,13 @@ __device__ inline void ecmult_double(gej &R, const sc &gs, const sc &ps,
 #define KV_DP2(w) glv_digit(p2h, w)
 #define KV_DN2(w) (p2h.neg)
 #endif
+  /* window 32 alone: the G digit sits at even position 32, and R starts at
+   * infinity, so this frame has adds only */
+  gej_window_first(R, ptab, lc, glv_digit8(g1h, 32), g1h.neg,
+                   glv_digit8(g2h, 32), g2h.neg, KV_DP1(32), KV_DN1(32),
+                   KV_DP2(32), KV_DN2(32));
 #if defined(KV_QUAD_WINDOWS)
-  /* window 32 alone, then 8 quad frames (two pairs each) */
-  gej_window_step(R, ptab, beta, 1, glv_digit8(g1h, 32), g1h.neg,
-                  glv_digit8(g2h, 32), g2h.neg, KV_DP1(32), KV_DN1(32),
-                  KV_DP2(32), KV_DN2(32));
+  /* 8 quad frames (two pairs each) */
 #pragma unroll 1
   for (int w = 31; w >= 3; w -= 4) {
     u64 a[12] = {glv_digit8(g1h, w - 1), g1h.neg, glv_digit8(g2h, w - 1),
@@ -569,16 +543,13 @@ __device__ inline void ecmult_double(gej &R, const sc &gs, const sc &ps,
     u64 b[12] = {glv_digit8(g1h, w - 3), g1h.neg, glv_digit8(g2h, w - 3),
                  g2h.neg, KV_DP1(w - 2), KV_DN1(w - 2), KV_DP2(w - 2), KV_DN2(w - 2),
                  KV_DP1(w - 3), KV_DN1(w - 3), KV_DP2(w - 3), KV_DN2(w - 3)};
-    gej_window_step4(R, ptab, beta, a, b);
+    gej_window_step4(R, ptab, lc, a, b);
   }
 #elif defined(KV_PAIR_WINDOWS)
-  /* window 32 alone (G digit at even position 32), then 16 window pairs */
-  gej_window_step(R, ptab, beta, 1, glv_digit8(g1h, 32), g1h.neg,
-                  glv_digit8(g2h, 32), g2h.neg, KV_DP1(32), KV_DN1(32),
-                  KV_DP2(32), KV_DN2(32));
+  /* 16 window pairs */
 #pragma unroll 1
   for (int w = 31; w >= 1; w -= 2) {
-    gej_window_step2(R, ptab, beta,
+    gej_window_step2(R, ptab, lc,
                      glv_digit8(g1h, w - 1), g1h.neg,
                      glv_digit8(g2h, w - 1), g2h.neg,
                      KV_DP1(w), KV_DN1(w), KV_DP2(w), KV_DN2(w),
@@ -586,9 +557,9 @@ __device__ inline void ecmult_double(gej &R, const sc &gs, const sc &ps,
   }
 #else
 #pragma unroll 1
-  for (int w = 32; w >= 0; w--) {
+  for (int w = 31; w >= 0; w--) {
     u64 g_active = (w & 1) == 0; /* 8-bit G digits at even window positions */
-    gej_window_step(R, ptab, beta, g_active,
+    gej_window_step(R, ptab, lc, g_active,
                     g_active ? glv_digit8(g1h, w) : 0, g1h.neg,
                     g_active ? glv_digit8(g2h, w) : 0, g2h.neg,
                     KV_DP1(w), KV_DN1(w), KV_DP2(w), KV_DN2(w));
@@ -598,7 +569,11 @@ __device__ inline void ecmult_double(gej &R, const sc &gs, const sc &ps,
 #undef KV_DN1
 #undef KV_DP2
 #undef KV_DN2
-#undef KV_PTAB_MAX
+  /* back from the isomorphic curve: (X, Y, Z) there is (X, Y, Z·Zg) on
+   * secp256k1 (infinity keeps z == 0) */
+  fe26 rz;
+  fe26_mul(rz, R.z, zg);
+  R.z = rz;
 }
 
 /* One BIP-340 verification; returns KVS_* */
