@@ -213,6 +213,12 @@ int kv_stage_tuples(kv_ctx *ctx, const uint8_t *tuples, size_t n, int ecdsa);
 int kv_verify_staged(kv_ctx *ctx, size_t n, int ecdsa, double *kernel_ms);
 int kv_fetch_bitmap(kv_ctx *ctx, size_t n, uint64_t *bitmap_out);
 
+/* Schnorr batches of at least KV_SCHNORR_SPLIT_MIN signatures (environment,
+ * read once in kv_create; a built-in default otherwise) run as a ladder kernel
+ * plus a finish kernel that inverts K signatures per lane in one batch. Same
+ * outputs as the fused kernel. Returns K as compiled. */
+int kv_schnorr_finish_batch(void);
+
 /* ---- GPU-resident UTXO set ----
  * ⇔ UtxoCollection (consensus/core/src/utxo/utxo_collection.rs:5) + the
  * populate/diff steps (utxo_validation.rs:351-390, utxo_diff.rs:224).

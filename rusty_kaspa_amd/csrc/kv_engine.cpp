@@ -61,6 +61,16 @@ struct kv_sig_key_hash {
   size_t operator()(const kv_sig_key &k) const { return (size_t)k.w[0]; }
 };
 
+/* Batches of at least this many signatures run the ladder and the batched
+ * finish as two kernels; smaller ones keep the fused kernel (a block-path batch
+ * of ~10k signatures is latency-bound and gains nothing from a second launch).
+ * Measured crossover: fused is ahead up to 131,072, split from
+ * 262,144 on. KV_SCHNORR_SPLIT_MIN in the environment, read once in kv_create,
+ * overrides it: 1 forces the split path, a huge value the fused one. */
+#ifndef KV_SCHNORR_SPLIT_MIN_DEFAULT
+#define KV_SCHNORR_SPLIT_MIN_DEFAULT ((size_t)1 << 18)
+#endif
+
 struct kv_ctx {
   kv_params params;
   hipStream_t stream;
@@ -130,6 +140,12 @@ struct kv_ctx {
   size_t d_val_cap = 0;
   uint8_t *d_ent_out = nullptr;
   size_t d_ent_cap = 0;
+  /* split Schnorr verify (launch_schnorr_verify): the ladder kernel's R limbs
+   * and pre-status, 121 B per signature. Written and read on ctx->stream only,
+   * under ctx->mu. */
+  uint8_t *d_sfin = nullptr;
+  size_t d_sfin_cap = 0;
+  size_t schnorr_split_min = KV_SCHNORR_SPLIT_MIN_DEFAULT;
 };
 
 static int ensure_cap(void **ptr, size_t *cap, size_t need) {
@@ -170,6 +186,11 @@ extern "C" kv_ctx *kv_create(const kv_params *params) {
     delete ctx;
     return nullptr;
   }
+  if (const char *e = getenv("KV_SCHNORR_SPLIT_MIN")) {
+    char *end = nullptr;
+    unsigned long long v = strtoull(e, &end, 10);
+    if (end != e && v > 0) ctx->schnorr_split_min = (size_t)v;
+  }
   /* fill the shared affine G multiples table (idempotent, once per device) */
   hipLaunchKernelGGL(kv::kv_ec_table_init_kernel, dim3(1), dim3(64), 0, ctx->stream);
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
@@ -209,6 +230,7 @@ extern "C" void kv_destroy(kv_ctx *ctx) {
   if (ctx->d_op_in) (void)hipFree(ctx->d_op_in);
   if (ctx->d_val_in) (void)hipFree(ctx->d_val_in);
   if (ctx->d_ent_out) (void)hipFree(ctx->d_ent_out);
+  if (ctx->d_sfin) (void)hipFree(ctx->d_sfin);
   (void)hipGetLastError(); /* teardown calls are fire-and-forget; do not leave
       their errors sticky for the next engine's launch checks (a swallowed
       invalid-argument here surfaced as a spurious failure in the NEXT
@@ -217,6 +239,35 @@ extern "C" void kv_destroy(kv_ctx *ctx) {
 }
 
 /* ---------------- batched verify entry points ---------------- */
+
+/* Every Schnorr verify launch goes through here (ctx->mu held, ctx->stream):
+ * the fused kernel below the split threshold, else ladder + batched finish
+ * back to back on the same stream. Same outputs either way. */
+static int launch_schnorr_verify(kv_ctx *ctx, const uint8_t *d_tuples, size_t n,
+                                 unsigned long long *d_bitmap, uint8_t *d_status) {
+  if (n == 0) return 0;
+  const unsigned long long grid = (n + 255) / 256;
+  if (n < ctx->schnorr_split_min) {
+    hipLaunchKernelGGL(kv::kv_schnorr_verify_kernel, dim3(grid), dim3(256), 0,
+                       ctx->stream, d_tuples, (unsigned long long)n, d_bitmap,
+                       d_status);
+    return 0;
+  }
+  if (ensure_cap((void **)&ctx->d_sfin, &ctx->d_sfin_cap, n * 121)) return -2;
+  kv::u32 *limbs = (kv::u32 *)ctx->d_sfin;
+  uint8_t *pre = ctx->d_sfin + n * 120;
+  hipLaunchKernelGGL(kv::kv_schnorr_ladder_kernel, dim3(grid), dim3(256), 0,
+                     ctx->stream, d_tuples, (unsigned long long)n, limbs, pre);
+  const unsigned long long lanes =
+      ((n + KV_FINISH_K - 1) / KV_FINISH_K + 63) / 64 * 64;
+  hipLaunchKernelGGL(kv::kv_schnorr_finish_kernel, dim3(lanes / 64), dim3(64), 0,
+                     ctx->stream, d_tuples, (unsigned long long)n,
+                     (const kv::u32 *)limbs, (const uint8_t *)pre, lanes, d_bitmap,
+                     d_status);
+  return 0;
+}
+
+extern "C" int kv_schnorr_finish_batch(void) { return KV_FINISH_K; }
 
 static int verify_batch(kv_ctx *ctx, const uint8_t *tuples, size_t n, size_t rec_size,
                         int ecdsa, uint64_t *bitmap_out, uint8_t *status_out) {
@@ -237,10 +288,10 @@ static int verify_batch(kv_ctx *ctx, const uint8_t *tuples, size_t n, size_t rec
     hipLaunchKernelGGL(kv::kv_ecdsa_verify_kernel, dim3(grid), dim3(block), 0, ctx->stream,
                        ctx->d_in, (unsigned long long)n, (unsigned long long *)ctx->d_bitmap,
                        status_out ? ctx->d_status : nullptr);
-  else
-    hipLaunchKernelGGL(kv::kv_schnorr_verify_kernel, dim3(grid), dim3(block), 0, ctx->stream,
-                       ctx->d_in, (unsigned long long)n, (unsigned long long *)ctx->d_bitmap,
-                       status_out ? ctx->d_status : nullptr);
+  else if (launch_schnorr_verify(ctx, ctx->d_in, n,
+                                 (unsigned long long *)ctx->d_bitmap,
+                                 status_out ? ctx->d_status : nullptr))
+    return -2;
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(bitmap_out, ctx->d_bitmap, words * 8, hipMemcpyDeviceToHost,
                            ctx->stream));
@@ -470,10 +521,9 @@ extern "C" int kv_verify_staged(kv_ctx *ctx, size_t n, int ecdsa, double *kernel
     hipLaunchKernelGGL(kv::kv_ecdsa_verify_kernel, dim3(grid), dim3(block), 0,
                        ctx->stream, ctx->d_in, (unsigned long long)n,
                        (unsigned long long *)ctx->d_bitmap, nullptr);
-  else
-    hipLaunchKernelGGL(kv::kv_schnorr_verify_kernel, dim3(grid), dim3(block), 0,
-                       ctx->stream, ctx->d_in, (unsigned long long)n,
-                       (unsigned long long *)ctx->d_bitmap, nullptr);
+  else if (launch_schnorr_verify(ctx, ctx->d_in, n,
+                                 (unsigned long long *)ctx->d_bitmap, nullptr))
+    return -2; /* both kernels of the split path sit between t0 and t1 */
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipEventRecord(t1, ctx->stream));
   HIP_CHECK(hipEventSynchronize(t1));
@@ -1337,10 +1387,10 @@ static int validate_block_impl(kv_ctx *ctx, const uint8_t *blob, size_t blob_len
       tev_rec(ctx, 3);
       tev_rec_pair[1] = true;
       tev_rec(ctx, 6);
-      hipLaunchKernelGGL(kv::kv_schnorr_verify_kernel, dim3(((uint32_t)ns + 255) / 256),
-                         dim3(256), 0, ctx->stream, (const uint8_t *)vb.s_tuples.p,
-                         (unsigned long long)ns, (unsigned long long *)vb.s_bitmap.p,
-                         (uint8_t *)vb.s_status.p);
+      if (launch_schnorr_verify(ctx, (const uint8_t *)vb.s_tuples.p, ns,
+                                (unsigned long long *)vb.s_bitmap.p,
+                                (uint8_t *)vb.s_status.p))
+        return -2;
       tev_rec(ctx, 7);
       tev_rec_pair[3] = true;
       ctx->last_timings.n_schnorr += ns;
@@ -1557,12 +1607,10 @@ static int validate_block_impl(kv_ctx *ctx, const uint8_t *blob, size_t blob_len
                                (uint32_t)mjobs_s.size(),
                                (uint8_t *)vb.s_tuples.p, 128u, 96u);
           }
-          hipLaunchKernelGGL(kv::kv_schnorr_verify_kernel,
-                             dim3(((uint32_t)ns_i + 255) / 256), dim3(256), 0,
-                             ctx->stream, (const uint8_t *)vb.s_tuples.p,
-                             (unsigned long long)ns_i,
-                             (unsigned long long *)vb.s_bitmap.p,
-                             (uint8_t *)vb.s_status.p);
+          if (launch_schnorr_verify(ctx, (const uint8_t *)vb.s_tuples.p, ns_i,
+                                    (unsigned long long *)vb.s_bitmap.p,
+                                    (uint8_t *)vb.s_status.p))
+            return -2;
           HIP_CHECK(hipMemcpyAsync(s_st.data(), vb.s_status.p, ns_i,
                                    hipMemcpyDeviceToHost, ctx->stream));
         }

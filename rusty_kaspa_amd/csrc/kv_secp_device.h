@@ -149,7 +149,8 @@ __device__ __forceinline__ void fe_mul(fe &r, const fe &a, const fe &b) {
  * before transcription.
  *
  * Magnitude discipline (limb_i < m * 2^26, top < m * 2^26):
- *   - fe26_mul / fe26_sqr outputs: m = 1 (top limb may graze 2^26: m <= 2)
+ *   - fe26_mul / fe26_sqr outputs: m = 1 (limbs <= 2^26, top limb < 2^22; l2
+ *     may graze 2^26 by one, so count m <= 2 — see fe26_reduce19)
  *   - inputs to mul/sqr MUST have m <= 8
  *   - fe26_add: m = ma + mb;  fe26_neg(m): result m+1;  adds/subs may run to
  *     m <= 31 (u32 limb bound) before a fe26_norm_weak (-> m = 1)
@@ -180,48 +181,63 @@ struct fe26 {
 #endif
 
 __device__ __forceinline__ void fe26_reduce19(fe26 &r, const u64 t[19]) {
-  /* fold columns 10..18 into 0..12 via 2^260 == R0 + 2^36 (mod p)·2^(26k) */
-  u64 s[13];
-#pragma unroll
-  for (int k = 0; k < 10; k++) s[k] = t[k];
-  s[10] = s[11] = s[12] = 0;
+  /* Digit-first reduction. Input: the column sums of fe26_mul_inner /
+   * fe26_sqr_inner for operand limbs <= 2^30, so t[k] <= n_k * 2^60 with
+   * n_k = min(k + 1, 19 - k) products (t[9] <= 10*2^60 < 2^64, every other
+   * column <= 9*2^60). Output: l0, l1 < 2^26, l2 <= 2^26, l3..l8 < 2^26,
+   * l9 < 2^22 — magnitude 1 with l2 grazing 2^26 by at most one.
+   *
+   * 1. One carry sweep over the HIGH half (bits 26.. of t[9], then columns
+   *    10..18) turns it into 26-bit digits u[0..9] plus a small u[10]:
+   *    high half == sum u[k] * 2^(260 + 26k). Each d <= 9*2^60 + c with
+   *    c < 2^38 (a carry is a 64-bit value >> 26), so d < 2^64; the last carry
+   *    is <= (2^60 + 2^38) >> 26, so u[10] <= 2^8.
+   * 2. 2^260 == R0 + 2^36 (mod p), so digit u[k] lands as u[k]*R0 in column k
+   *    and u[k] << 10 in column k + 1: every fold operand is a 26-bit digit
+   *    and every fold term is < 2^40. u[9] and u[10] reach column 10 again:
+   *    W = (u9 << 10) + u10*R0 + (u10 << 36) < 2^36 + 2^22 + 2^44 < 2^45 is
+   *    folded once more as w0 = W mod 2^26 and w1 = W >> 26 < 2^19 into
+   *    columns 0..2 (terms < 2^40).
+   * 3. One sweep over the LOW half with the fold terms added on the way:
+   *    d <= 9*2^60 + 2^38 (carry) + 4 * 2^40 < 2^64. Column 9 takes only the
+   *    low 26 bits of t[9], so the carry out is cc < 2^15.
+   * 4. Bits 22.. of l9 and cc sit at 2^256 == 2^32 + 977: x < 2^19 + 2^4, so
+   *    x*977 < 2^29 and x << 6 < 2^26 fit u32 on top of a 26-bit digit; a
+   *    three-limb ripple leaves l0, l1 < 2^26 and adds at most 1 to l2. */
+  u32 u[11];
+  u64 c = t[9] >> 26;
 #pragma unroll
   for (int k = 0; k < 9; k++) {
-    u64 lo = t[k + 10] & KV26_M;
-    u64 hi = t[k + 10] >> 26;
-    s[k] += lo * KV26_R0;
-    s[k + 1] += (lo << 10) + hi * KV26_R0;
-    s[k + 2] += hi << 10;
-  }
-  u64 out[13], c = 0;
-#pragma unroll
-  for (int k = 0; k < 13; k++) {
-    u64 d = s[k] + c;
-    out[k] = d & KV26_M;
+    u64 d = t[k + 10] + c;
+    u[k] = (u32)d & KV26_M;
     c = d >> 26;
   }
-  /* second fold: tiny spill in out[10..12] */
-  u64 extra = out[10] | (out[11] << 26) | (out[12] << 52);
-  u64 lo = extra & KV26_M, hi = extra >> 26;
-  out[0] += lo * KV26_R0;
-  out[1] += (lo << 10) + hi * KV26_R0;
-  out[2] += hi << 10;
-  c = 0;
+  u[9] = (u32)c & KV26_M;
+  u[10] = (u32)(c >> 26);
+  u64 W = ((u64)u[9] << 10) + (u64)u[10] * KV26_R0 + ((u64)u[10] << 36);
+  u32 w0 = (u32)W & KV26_M, w1 = (u32)(W >> 26);
+  u64 cc = 0;
 #pragma unroll
   for (int k = 0; k < 10; k++) {
-    u64 d = out[k] + c;
-    r.l[k] = (u32)(d & KV26_M);
-    c = d >> 26;
+    u64 d = (k == 9 ? (t[9] & KV26_M) : t[k]) + cc + (u64)u[k] * KV26_R0;
+    if (k >= 1) d += (u64)u[k - 1] << 10;
+    if (k == 0) d += (u64)w0 * KV26_R0;
+    if (k == 1) d += ((u64)w0 << 10) + (u64)w1 * KV26_R0;
+    if (k == 2) d += (u64)w1 << 10;
+    r.l[k] = (u32)d & KV26_M;
+    cc = d >> 26;
   }
-  /* residual carry (tiny): 2^260 fold once more */
-  r.l[0] += (u32)(c * KV26_R0);
-  r.l[1] += (u32)(c << 10);
-  /* keep the top limb 22-bit (the magnitude convention scales l9 by 2^22):
-   * x*2^256 == x*(2^32 + 977) */
-  u32 x = r.l[9] >> 22;
+#ifdef KV_HOST_TEST
+  assert(u[10] <= (1u << 8) && W < ((u64)1 << 45) && cc < (1u << 15));
+#endif
+  /* keep the top limb 22-bit (the magnitude convention scales l9 by 2^22) */
+  u32 x = (r.l[9] >> 22) + ((u32)cc << 4);
   r.l[9] &= 0x3FFFFF;
   r.l[0] += x * 977u;
-  r.l[1] += x << 6;
+  r.l[1] += (x << 6) + (r.l[0] >> 26);
+  r.l[0] &= KV26_M;
+  r.l[2] += r.l[1] >> 26;
+  r.l[1] &= KV26_M;
 }
 
 __device__ __forceinline__ void fe26_mul_inner(u64 t[19], const fe26 &a,

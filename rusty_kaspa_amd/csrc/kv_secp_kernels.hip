@@ -576,15 +576,18 @@ __device__ inline void ecmult_double(gej &R, const sc &gs, const sc &ps,
   R.z = rz;
 }
 
-/* One BIP-340 verification; returns KVS_* */
-__device__ inline uint8_t schnorr_verify_one(const uint8_t *rb, const uint8_t *sb,
-                                             const uint8_t *pkb, const uint8_t *msg) {
+/* A BIP-340 verification up to and including the ladder: parses the tuple and
+ * computes R = s·G - e·P (Jacobian). Returns 0 when the verdict is still
+ * pending on R, else the final KVS_* code of an early exit. rx is r as a field
+ * element (canonical limbs), valid when 0 is returned. */
+__device__ inline uint8_t schnorr_ladder_one(gej &R, fe26 &rx, const uint8_t *rb,
+                                             const uint8_t *sb, const uint8_t *pkb,
+                                             const uint8_t *msg) {
   ge P;
   if (!lift_x_even(P, pkb)) return KVS_BAD_PUBKEY;
   fe rxu;
   fe_from_be(rxu, rb);
   if (fe_gte_p_full(rxu)) return KVS_INVALID;
-  fe26 rx;
   fe26_from_fe(rx, rxu);
   sc s;
   if (sc_from_be(s, sb)) return KVS_INVALID;
@@ -593,12 +596,16 @@ __device__ inline uint8_t schnorr_verify_one(const uint8_t *rb, const uint8_t *s
   sc e, ne;
   sc_from_be(e, eh);
   sc_neg(ne, e);
-  gej R;
   ecmult_double(R, s, ne, P);
-  if (gej_is_infinity(R)) return KVS_INVALID;
-  /* affine via one inversion: need x == r and even y */
-  fe26 zi, zi2, zi3, xa, ya;
-  fe26_inv(zi, R.z);
+  return 0;
+}
+
+/* The verdict from R's affine coordinates, given zi = 1/R.z: x == r and even
+ * y. Five field operations. */
+__device__ __forceinline__ uint8_t schnorr_affine_verdict(const gej &R,
+                                                          const fe26 &zi,
+                                                          const fe26 &rx) {
+  fe26 zi2, zi3, xa, ya;
   fe26_sqr(zi2, zi);
   fe26_mul(zi3, zi2, zi);
   fe26_mul(xa, R.x, zi2);
@@ -606,6 +613,108 @@ __device__ inline uint8_t schnorr_verify_one(const uint8_t *rb, const uint8_t *s
   fe26_normalize(ya);
   if (ya.l[0] & 1) return KVS_INVALID;
   return fe26_eq(xa, rx) ? KVS_VALID : KVS_INVALID;
+}
+
+/* One BIP-340 verification; returns KVS_* */
+__device__ inline uint8_t schnorr_verify_one(const uint8_t *rb, const uint8_t *sb,
+                                             const uint8_t *pkb, const uint8_t *msg) {
+  gej R;
+  fe26 rx;
+  uint8_t pre = schnorr_ladder_one(R, rx, rb, sb, pkb, msg);
+  if (pre) return pre;
+  if (gej_is_infinity(R)) return KVS_INVALID;
+  /* affine via one inversion */
+  fe26 zi;
+  fe26_inv(zi, R.z);
+  return schnorr_affine_verdict(R, zi, rx);
+}
+
+/* ---------------- split verify: ladder kernel + batched finish ----------------
+ * The Fermat inversion above (255 squarings + 15 multiplies) serves one parity
+ * bit per signature. Large batches run the ladder and the finish as two
+ * kernels: the ladder kernel leaves R in HBM, and the finish kernel inverts K
+ * signatures' R.z per LANE with Montgomery's trick (one inversion plus three
+ * multiplies per value). Batching has to be per lane: a wave pays for the
+ * chain whether one lane or 64 run it.
+ *
+ * Intermediate buffer, 121 B per signature: 30 u32 limbs (R.x, R.y, R.z) as
+ * structure-of-arrays, limb j of signature i at limbs[j*n + i], then n
+ * pre-status bytes (0 = pending, else the final KVS_* code). Limbs of a
+ * non-pending entry are never written and never enter arithmetic. */
+#ifndef KV_FINISH_K
+#define KV_FINISH_K 16
+#endif
+
+__device__ __forceinline__ void fin_load26(fe26 &v, const u32 *__restrict__ limbs,
+                                           unsigned long long n, int coord,
+                                           unsigned long long i) {
+#pragma unroll
+  for (int j = 0; j < 10; j++) v.l[j] = limbs[(unsigned long long)(10 * coord + j) * n + i];
+}
+
+/* z of entry i for the batch product: R.z, or 1 where no inversion is wanted
+ * (code != 0). Branch-free. */
+__device__ __forceinline__ void fin_load_z(fe26 &z, const u32 *__restrict__ limbs,
+                                           unsigned long long n,
+                                           unsigned long long i, uint8_t code) {
+  fe26 one;
+  fe26_set_int(one, 1);
+  fin_load26(z, limbs, n, 2, i);
+  fe26_cmov(z, one, (u32)(code != 0));
+}
+
+/* The finish of one lane: entries i = first + m*step, m < KV_FINISH_K. st[m]
+ * receives the final KVS_* code of entry m (KVS_INVALID for i >= n, which the
+ * caller does not publish). Entries that are not pending, out of range or at
+ * infinity (z == 0 mod p, verdict KVS_INVALID) enter the product as 1, so
+ * their neighbours' inverses are untouched. */
+__device__ inline void schnorr_finish_lane(uint8_t st[KV_FINISH_K],
+                                           const u32 *__restrict__ limbs,
+                                           const uint8_t *__restrict__ pre,
+                                           const uint8_t *__restrict__ tuples,
+                                           unsigned long long n,
+                                           unsigned long long first,
+                                           unsigned long long step) {
+  fe26 pref[KV_FINISH_K]; /* pref[m] = z_0 · … · z_{m-1} */
+  fe26 acc, one;
+  fe26_set_int(acc, 1);
+  fe26_set_int(one, 1);
+#pragma unroll 1
+  for (int m = 0; m < KV_FINISH_K; m++) {
+    unsigned long long i = first + (unsigned long long)m * step;
+    u32 inr = i < n;
+    unsigned long long ii = inr ? i : n - 1; /* clamped: loads stay in bounds */
+    uint8_t code = inr ? pre[ii] : (uint8_t)KVS_INVALID;
+    fe26 z;
+    fin_load_z(z, limbs, n, ii, code);
+    u32 inf = (u32)fe26_normalizes_to_zero(z); /* z is a mul output: <= 2 */
+    fe26_cmov(z, one, inf);
+    st[m] = inf ? (uint8_t)KVS_INVALID : code;
+    pref[m] = acc;
+    fe26_mul(acc, acc, z);
+  }
+  fe26 inv;
+  fe26_inv(inv, acc); /* acc != 0: every factor is a non-zero residue */
+#pragma unroll 1
+  for (int m = KV_FINISH_K - 1; m >= 0; m--) {
+    unsigned long long i = first + (unsigned long long)m * step;
+    unsigned long long ii = i < n ? i : n - 1;
+    uint8_t code = st[m];
+    fe26 z, zi;
+    fin_load_z(z, limbs, n, ii, code);
+    fe26_mul(zi, inv, pref[m]); /* 1/z_m */
+    fe26_mul(inv, inv, z);      /* 1/(z_0 · … · z_{m-1}) */
+    if (code == 0) {
+      gej R;
+      fin_load26(R.x, limbs, n, 0, ii);
+      fin_load26(R.y, limbs, n, 1, ii);
+      fe rxu;
+      fe_from_be(rxu, tuples + ii * 128); /* r < p: the ladder checked it */
+      fe26 rx;
+      fe26_from_fe(rx, rxu);
+      st[m] = schnorr_affine_verdict(R, zi, rx);
+    }
+  }
 }
 
 #ifndef KV_LB
@@ -632,6 +741,54 @@ extern "C" __global__ void KV_LB kv_schnorr_verify_kernel(const uint8_t *__restr
     if (i < n) bitmap[word] = mask;
   }
 }
+
+#ifndef KV_HOST_TEST
+extern "C" __global__ void KV_LB kv_schnorr_ladder_kernel(const uint8_t *__restrict__ tuples,
+                                                    unsigned long long n,
+                                                    u32 *__restrict__ limbs,
+                                                    uint8_t *__restrict__ pre) {
+  unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t *t = tuples + i * 128;
+  gej R;
+  fe26 rx;
+  uint8_t st = schnorr_ladder_one(R, rx, t, t + 32, t + 64, t + 96);
+  pre[i] = st;
+  if (st) return;
+#pragma unroll
+  for (int j = 0; j < 10; j++) {
+    limbs[(unsigned long long)j * n + i] = R.x.l[j];
+    limbs[(unsigned long long)(10 + j) * n + i] = R.y.l[j];
+    limbs[(unsigned long long)(20 + j) * n + i] = R.z.l[j];
+  }
+}
+
+/* Lane t of T lanes (T a multiple of 64, T*KV_FINISH_K >= n, grid = T/64
+ * blocks of 64) finishes signatures m*T + t: for each m the 64 lanes of a wave
+ * hold 64 consecutive signatures, so one ballot is one whole bitmap word. */
+extern "C" __global__ void __launch_bounds__(64)
+kv_schnorr_finish_kernel(const uint8_t *__restrict__ tuples, unsigned long long n,
+                         const u32 *__restrict__ limbs,
+                         const uint8_t *__restrict__ pre, unsigned long long T,
+                         unsigned long long *__restrict__ bitmap,
+                         uint8_t *__restrict__ status) {
+  unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  uint8_t st[KV_FINISH_K];
+  schnorr_finish_lane(st, limbs, pre, tuples, n, t, T);
+#pragma unroll 1
+  for (int m = 0; m < KV_FINISH_K; m++) {
+    unsigned long long i = (unsigned long long)m * T + t;
+    int valid = 0;
+    if (i < n) {
+      if (status) status[i] = st[m];
+      valid = (st[m] == KVS_VALID);
+    }
+    unsigned long long mask = __ballot(valid);
+    /* lane 0's index is 64-aligned; i < n keeps the store below `words` */
+    if ((threadIdx.x & 63) == 0 && i < n) bitmap[i / 64] = mask;
+  }
+}
+#endif /* !KV_HOST_TEST */
 
 /* ---------------- ECDSA ---------------- */
 
