@@ -21,6 +21,15 @@
  *   kv_sighash_batch        ⇔ calc_schnorr_signature_hash / calc_ecdsa_signature_hash
  *                             (consensus/core/src/hashing/sighash.rs:245-292)
  *   kv_muhash_finalize      ⇔ MuHash::finalize (crypto/muhash/src/lib.rs:93)
+ *   kv_utxo_commitment      ⇔ the multiset of the whole UTXO set that
+ *                             import_pruning_point_utxo_set checks against the
+ *                             header (consensus/src/pipeline/virtual_processor/
+ *                             processor.rs:1525-1538) and that
+ *                             verify_expected_utxo_state implies per block
+ *                             (utxo_validation.rs:188-195)
+ *   kv_utxo_commitment_window  slots per scan window of kv_utxo_commitment
+ *   kv_utxo_import_chunk    ⇔ Consensus::append_imported_pruning_point_utxos
+ *                             (consensus/src/consensus/mod.rs:1139-1152)
  *
  * No torch types cross this boundary: plain pointers and sizes only.
  * See INTEGRATION.md for the Rust-side binding a maintainer would add.
@@ -258,6 +267,59 @@ int kv_utxo_lookup(kv_ctx *ctx, const uint8_t *outpoints, size_t n,
 int kv_utxo_lookup_spk(kv_ctx *ctx, const uint8_t *outpoints, size_t n,
                        uint8_t *entries_out, uint64_t *found_bitmap,
                        uint8_t *spk_out, size_t spk_cap, size_t *spk_used);
+
+/* ---- UTXO-set MuHash commitment ----
+ * An entry's element is MuHash::from_utxo over write_utxo
+ * (consensus/core/src/muhash.rs:55-69): tx_id ‖ index u32 ‖ daa_score u64 ‖
+ * amount u64 ‖ is_coinbase u8 ‖ spk_version u16 ‖ spk_len u64 ‖ spk. Arena
+ * scripts are hashed in place. The table stores no covenant ids (covenant
+ * outputs are KV_ERR_BAD_BLOB on the table path), so none is hashed. */
+
+/* ⇔ MuHash over every live entry of the GPU-resident set
+ *   (import_pruning_point_utxo_set's multiset, consensus/src/pipeline/
+ *   virtual_processor/processor.rs:1525-1538; verify_expected_utxo_state,
+ *   utxo_validation.rs:188-195).
+ * partial768_out: numerator = product of every READY slot's element mod
+ * 2^3072-1103717 (not necessarily canonical), denominator = 1. An empty or
+ * never-reset table gives the identity partial and n_live = 0. Read-only on
+ * the table; takes the context lock and is stream-ordered after earlier
+ * upserts and removes. kernel_ms is hipEvent time over the whole chain.
+ *  - Bounded scratch: the table is scanned in windows of
+ *    kv_utxo_commitment_window() slots. Device scratch is 4 B + 384 B per
+ *    window slot (index list, elements), 4096 × 384 B of running accumulators
+ *    and under 1 MB for the final reduce — a function of the compiled window,
+ *    never of table capacity.
+ *  - No per-window host round trip: every window's compact → hash → fold
+ *    kernels read the window's live count from device memory; the whole chain
+ *    enqueues on the stream, is synchronised once at the end, and one 400 B
+ *    record (384 B value, count, status) is copied back.
+ *  - Only live slots cost hashing: READY slots are compacted first (wave
+ *    ballot + one atomic per wave), so EMPTY and TOMB slots never reach
+ *    BLAKE2b/ChaCha or the multiply chain.
+ * Returns -3 if a READY entry's script reference lies outside the arena. */
+int kv_utxo_commitment(kv_ctx *ctx, uint8_t partial768_out[768],
+                       uint64_t *n_live_out /*optional*/, double *kernel_ms /*optional*/);
+int kv_utxo_commitment_window(void); /* slots per scan window, as compiled */
+
+/* ⇔ Consensus::append_imported_pruning_point_utxos
+ *   (consensus/src/consensus/mod.rs:1139-1152): store the chunk AND fold
+ *   MuHash::from_utxo of each of its entries into a running multiset.
+ * Inputs and table effect are exactly those of kv_utxo_upsert_spk. In
+ * addition the product of the chunk's n elements is multiplied into the
+ * numerator half of acc_partial768; the denominator half is untouched. The
+ * elements are computed from the chunk as staged on the device, after the
+ * arena rewrite (long scripts are read from the arena), not from a table
+ * scan. n == 0 is a no-op returning 0; on any error the accumulator is
+ * unchanged. Start from the identity partial (num = den = 1) and compare
+ * kv_muhash_finalize of the accumulator with the header's utxo_commitment.
+ * Duplicates: an outpoint that occurs twice across chunks (or within one) is
+ * counted twice in the multiset but stored once in the table — as in the
+ * reference, where write_many overwrites while the multiset keeps both. With
+ * distinct outpoints imported into a fresh table, kv_utxo_commitment equals
+ * the accumulator. */
+int kv_utxo_import_chunk(kv_ctx *ctx, const uint8_t *outpoints, const uint8_t *entries64,
+                         const uint8_t *spk_blob, size_t spk_blob_len, size_t n,
+                         uint8_t acc_partial768[768] /* in/out */);
 
 /* Populate + validate + (optionally) apply the UTXO diff — the full virtual
  * processor step for one block (utxo_validation.rs:351-390 populate, then

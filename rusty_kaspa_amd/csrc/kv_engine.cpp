@@ -26,6 +26,7 @@
 #include "kv_secp_kernels.hip"
 #include "kv_sighash_kernels.hip"
 #include "kv_utxo_kernels.hip"
+#include "kv_utxo_commit_kernels.hip"
 #include "kv_validate_host.inc"
 #include "kv_script_host.inc"
 
@@ -140,6 +141,13 @@ struct kv_ctx {
   size_t d_val_cap = 0;
   uint8_t *d_ent_out = nullptr;
   size_t d_ent_cap = 0;
+  /* UTXO commitment scratch (kv_utxo_commit_kernels.hip): sized by the
+   * compiled window, never by table capacity. d_cm_fixed holds, in order, the
+   * copy-back record, the window's live count, the slot index list, the
+   * running accumulators and the final reduce's two partial buffers. */
+  uint8_t *d_cm_fixed = nullptr;
+  uint64_t *d_cm_elems = nullptr;
+  size_t d_cm_elems_cap = 0;
   /* split Schnorr verify (launch_schnorr_verify): the ladder kernel's R limbs
    * and pre-status, 121 B per signature. Written and read on ctx->stream only,
    * under ctx->mu. */
@@ -231,6 +239,8 @@ extern "C" void kv_destroy(kv_ctx *ctx) {
   if (ctx->d_val_in) (void)hipFree(ctx->d_val_in);
   if (ctx->d_ent_out) (void)hipFree(ctx->d_ent_out);
   if (ctx->d_sfin) (void)hipFree(ctx->d_sfin);
+  if (ctx->d_cm_fixed) (void)hipFree(ctx->d_cm_fixed);
+  if (ctx->d_cm_elems) (void)hipFree(ctx->d_cm_elems);
   (void)hipGetLastError(); /* teardown calls are fire-and-forget; do not leave
       their errors sticky for the next engine's launch checks (a swallowed
       invalid-argument here surfaced as a spurious failure in the NEXT
@@ -2083,6 +2093,204 @@ extern "C" int kv_utxo_lookup(kv_ctx *ctx, const uint8_t *outpoints, size_t n,
       launch-config checks below only see THIS call's launches */
   return utxo_lookup_nolock(ctx, outpoints, n, entries_out, found_bitmap,
                             kernel_ms);
+}
+
+/* ---------------- UTXO-set commitment (kv_utxo_commit_kernels.hip) -----------
+ * ⇔ the pruning-point import multiset (consensus/mod.rs:1139-1152,
+ * processor.rs:1525-1538) and verify_expected_utxo_state
+ * (utxo_validation.rs:188-195). */
+
+namespace {
+constexpr size_t CM_OFF_OUT = 0;      /* kv::commit_out */
+constexpr size_t CM_OFF_COUNT = 512;  /* u32 live count of the current window */
+constexpr size_t CM_OFF_IDX = 1024;   /* u32[KV_COMMIT_WINDOW] */
+constexpr size_t CM_OFF_ACC = CM_OFF_IDX + (size_t)KV_COMMIT_WINDOW * 4;
+constexpr size_t CM_OFF_PA = CM_OFF_ACC + (size_t)KV_COMMIT_LANES * KVU_LIMBS * 8;
+constexpr size_t CM_OFF_PB = CM_OFF_PA + (size_t)1024 * KVU_LIMBS * 8;
+constexpr size_t CM_FIXED_BYTES = CM_OFF_PB + (size_t)1024 * KVU_LIMBS * 8;
+static_assert(sizeof(kv::commit_out) <= CM_OFF_COUNT, "commit_out outgrew its pad");
+static_assert((KV_COMMIT_WINDOW & (KV_COMMIT_WINDOW - 1)) == 0 &&
+                  KV_COMMIT_WINDOW >= 256,
+              "KV_COMMIT_WINDOW must be a power of two >= 256");
+} // namespace
+
+extern "C" int kv_utxo_commitment_window(void) { return (int)KV_COMMIT_WINDOW; }
+
+/* scratch for n_elems (<= KV_COMMIT_WINDOW) elements; the fixed part is one
+ * allocation whose size depends on the compiled window alone */
+static int commit_scratch(kv_ctx *ctx, size_t n_elems) {
+  if (!ctx->d_cm_fixed &&
+      hipMalloc(&ctx->d_cm_fixed, CM_FIXED_BYTES) != hipSuccess) {
+    ctx->d_cm_fixed = nullptr;
+    set_error("kv_utxo commitment: hipMalloc failed (scratch)");
+    return -2;
+  }
+  return ensure_cap((void **)&ctx->d_cm_elems, &ctx->d_cm_elems_cap,
+                    n_elems * KVU_LIMBS * 8);
+}
+
+/* zero the copy-back record and set `lanes` running accumulators to one */
+static int commit_begin(kv_ctx *ctx, uint32_t lanes) {
+  HIP_CHECK(hipMemsetAsync(ctx->d_cm_fixed + CM_OFF_OUT, 0, CM_OFF_COUNT,
+                           ctx->stream));
+  hipLaunchKernelGGL(kv::kv_u3072_fill_one_kernel,
+                     dim3((lanes * KVU_LIMBS + 255) / 256), dim3(256), 0,
+                     ctx->stream, (uint64_t *)(ctx->d_cm_fixed + CM_OFF_ACC), lanes);
+  return 0;
+}
+
+/* reduce the `lanes` accumulators to one value (host-known counts, the stride
+ * schedule of enqueue_muhash), move it into the copy-back record and queue the
+ * ONE device->host copy of the chain. The caller synchronises. */
+static int commit_finish(kv_ctx *ctx, uint32_t lanes, kv::commit_out *h_out) {
+  uint64_t *cur = (uint64_t *)(ctx->d_cm_fixed + CM_OFF_ACC);
+  uint64_t *pa = (uint64_t *)(ctx->d_cm_fixed + CM_OFF_PA);
+  uint64_t *pb = (uint64_t *)(ctx->d_cm_fixed + CM_OFF_PB);
+  uint32_t n_cur = lanes;
+  while (n_cur > 1) {
+    uint32_t stride = n_cur > 64 ? (n_cur + 63) / 64 : 1;
+    if (stride > 1024) stride = 1024;
+    hipLaunchKernelGGL(kv_u3072_reduce_wave_kernel, dim3((stride + 3) / 4),
+                       dim3(256), 0, ctx->stream, cur, n_cur, stride, pa);
+    n_cur = stride;
+    cur = pa;
+    std::swap(pa, pb);
+  }
+  kv::commit_out *d_out = (kv::commit_out *)(ctx->d_cm_fixed + CM_OFF_OUT);
+  hipLaunchKernelGGL(kv::kv_u3072_commit_out_kernel, dim3(1), dim3(64), 0,
+                     ctx->stream, cur, d_out);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(h_out, d_out, sizeof(kv::commit_out),
+                           hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
+}
+
+extern "C" int kv_utxo_commitment(kv_ctx *ctx, uint8_t partial768_out[768],
+                                  uint64_t *n_live_out, double *kernel_ms) {
+  if (!ctx || !partial768_out) {
+    set_error("kv_utxo_commitment: null argument");
+    return -1;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  (void)hipGetLastError(); /* clear any stale per-thread error so the
+      launch-config checks below only see THIS call's launches */
+  kv::u3072 one;
+  kv::u3072_one(one);
+  memcpy(partial768_out + 384, one.l, 384); /* denominator is always one */
+  if (n_live_out) *n_live_out = 0;
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (!ctx->d_utxo) { /* never reset: the empty set */
+    memcpy(partial768_out, one.l, 384);
+    return 0;
+  }
+  int rc = commit_scratch(ctx, KV_COMMIT_WINDOW);
+  if (rc) return rc;
+  uint8_t *fx = ctx->d_cm_fixed;
+  kv::commit_out *d_out = (kv::commit_out *)(fx + CM_OFF_OUT);
+  uint32_t *d_count = (uint32_t *)(fx + CM_OFF_COUNT);
+  uint32_t *d_idx = (uint32_t *)(fx + CM_OFF_IDX);
+  uint64_t *d_acc = (uint64_t *)(fx + CM_OFF_ACC);
+  hipEvent_t t0, t1;
+  HIP_CHECK(hipEventCreate(&t0));
+  HIP_CHECK(hipEventCreate(&t1));
+  HIP_CHECK(hipEventRecord(t0, ctx->stream));
+  rc = commit_begin(ctx, KV_COMMIT_LANES);
+  for (uint64_t base = 0; !rc && base < ctx->utxo_cap; base += KV_COMMIT_WINDOW) {
+    uint32_t n_slots = (uint32_t)std::min<uint64_t>(KV_COMMIT_WINDOW,
+                                                    ctx->utxo_cap - base);
+    dim3 grid((n_slots + 255) / 256);
+    if (hipMemsetAsync(d_count, 0, 16, ctx->stream) != hipSuccess) rc = -2;
+    hipLaunchKernelGGL(kv::kv_utxo_commit_compact_kernel, grid, dim3(256), 0,
+                       ctx->stream, ctx->d_utxo, base, n_slots, d_idx, d_count);
+    hipLaunchKernelGGL(kv::kv_utxo_commit_element_kernel, grid, dim3(256), 0,
+                       ctx->stream, ctx->d_utxo, base, (const uint32_t *)d_idx,
+                       (const uint32_t *)d_count, (const uint8_t *)ctx->d_arena,
+                       ctx->arena_head, ctx->d_cm_elems, d_out);
+    hipLaunchKernelGGL(kv_u3072_reduce_wave_acc_kernel,
+                       dim3(KV_COMMIT_LANES / 4), dim3(256), 0, ctx->stream,
+                       (const uint64_t *)ctx->d_cm_elems, (const uint32_t *)d_count,
+                       0u, KV_COMMIT_LANES, d_acc, d_out);
+  }
+  kv::commit_out h_out;
+  if (!rc) rc = commit_finish(ctx, KV_COMMIT_LANES, &h_out);
+  hipError_t e1 = hipEventRecord(t1, ctx->stream);
+  /* the single synchronisation of the chain */
+  hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  float ms = 0.f;
+  if (!rc && e1 == hipSuccess && e2 == hipSuccess)
+    (void)hipEventElapsedTime(&ms, t0, t1);
+  (void)hipEventDestroy(t0);
+  (void)hipEventDestroy(t1);
+  if (rc) return rc;
+  HIP_CHECK(e1);
+  HIP_CHECK(e2);
+  if (h_out.fail) {
+    set_error("kv_utxo_commitment: a table entry's script reference is out of range");
+    return -3;
+  }
+  memcpy(partial768_out, h_out.limbs, 384);
+  if (n_live_out) *n_live_out = h_out.n_live;
+  if (kernel_ms) *kernel_ms = ms;
+  return 0;
+}
+
+extern "C" int kv_utxo_import_chunk(kv_ctx *ctx, const uint8_t *outpoints,
+                                    const uint8_t *entries64, const uint8_t *spk_blob,
+                                    size_t spk_blob_len, size_t n,
+                                    uint8_t acc_partial768[768]) {
+  if (!ctx || !acc_partial768) {
+    set_error("kv_utxo_import_chunk: null argument");
+    return -1;
+  }
+  if (n == 0) return 0;
+  if (n > 0xffffffffu) {
+    set_error("kv_utxo_import_chunk: chunk too large");
+    return -1;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  (void)hipGetLastError(); /* clear any stale per-thread error so the
+      launch-config checks below only see THIS call's launches */
+  int rc = utxo_upsert_spk_nolock(ctx, outpoints, entries64, spk_blob,
+                                  spk_blob_len, n);
+  if (rc) return rc;
+  /* the chunk is still staged in d_op_in / d_val_in, long entries already
+   * rewritten to their arena offsets: hash it from there, scripts in place */
+  size_t batch = std::min<size_t>(n, KV_COMMIT_WINDOW);
+  rc = commit_scratch(ctx, batch);
+  if (rc) return rc;
+  uint8_t *fx = ctx->d_cm_fixed;
+  kv::commit_out *d_out = (kv::commit_out *)(fx + CM_OFF_OUT);
+  uint64_t *d_acc = (uint64_t *)(fx + CM_OFF_ACC);
+  /* about 8 elements per first-pass wave, at most KV_COMMIT_LANES waves */
+  uint32_t lanes = (uint32_t)std::min<size_t>((n + 7) / 8, KV_COMMIT_LANES);
+  rc = commit_begin(ctx, lanes);
+  if (rc) return rc;
+  for (size_t off = 0; off < n; off += batch) {
+    uint32_t m = (uint32_t)std::min(batch, n - off);
+    hipLaunchKernelGGL(kv::kv_utxo_chunk_element_kernel, dim3((m + 255) / 256),
+                       dim3(256), 0, ctx->stream,
+                       (const uint8_t *)ctx->d_op_in + off * 36,
+                       (const uint8_t *)ctx->d_val_in + off * 64, m,
+                       (const uint8_t *)ctx->d_arena, ctx->arena_head,
+                       ctx->d_cm_elems, d_out);
+    hipLaunchKernelGGL(kv_u3072_reduce_wave_acc_kernel, dim3((lanes + 3) / 4),
+                       dim3(256), 0, ctx->stream, (const uint64_t *)ctx->d_cm_elems,
+                       (const uint32_t *)nullptr, m, lanes, d_acc, d_out);
+  }
+  kv::commit_out h_out;
+  rc = commit_finish(ctx, lanes, &h_out);
+  if (rc) return rc;
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (h_out.fail) {
+    set_error("kv_utxo_import_chunk: an entry's script reference is out of range");
+    return -3;
+  }
+  u3072 prod, an, r;
+  memcpy(prod.l, h_out.limbs, 384);
+  memcpy(an.l, acc_partial768, 384);
+  kv::u3072_mulmod(r, an, prod);
+  memcpy(acc_partial768, r.l, 384);
+  return 0;
 }
 
 

@@ -133,6 +133,32 @@ class Engine:
         self._check(rc)
         return list(codes), list(fees), bytes(partial) if want_muhash else None
 
+    def utxo_commitment(self):
+        """MuHash partial over every live entry of the GPU-resident UTXO set:
+        (partial768, n_live, kernel_ms). The denominator half is one."""
+        partial = (ctypes.c_uint8 * 768)()
+        n_live = ctypes.c_uint64()
+        ms = ctypes.c_double()
+        rc = self.lib.kv_utxo_commitment(
+            ctypes.c_void_p(self.ctx), partial, ctypes.byref(n_live),
+            ctypes.byref(ms))
+        self._check(rc)
+        return bytes(partial), n_live.value, ms.value
+
+    def utxo_commitment_window(self) -> int:
+        """Slots per scan window of utxo_commitment, as compiled."""
+        return self.lib.kv_utxo_commitment_window()
+
+    def utxo_import_chunk(self, outpoints: bytes, entries64: bytes,
+                          spk_blob: bytes, n: int, acc: bytearray) -> None:
+        """kv_utxo_upsert_spk of the chunk, and its n elements multiplied into
+        the numerator half of the 768-byte accumulator `acc` (in place)."""
+        buf = (ctypes.c_uint8 * 768).from_buffer(acc)
+        rc = self.lib.kv_utxo_import_chunk(
+            ctypes.c_void_p(self.ctx), outpoints, entries64, spk_blob,
+            ctypes.c_size_t(len(spk_blob)), ctypes.c_size_t(n), buf)
+        self._check(rc)
+
     def sig_cache_stats(self):
         out = KvCacheStats()
         self._check(self.lib.kv_sig_cache_stats(ctypes.c_void_p(self.ctx),
