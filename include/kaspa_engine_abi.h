@@ -228,6 +228,12 @@ int kv_fetch_bitmap(kv_ctx *ctx, size_t n, uint64_t *bitmap_out);
  * outputs as the fused kernel. Returns K as compiled. */
 int kv_schnorr_finish_batch(void);
 
+/* Introspection: copies `count` 64-byte entries of the verify ladder's joint
+ * fixed-base table, from entry `first`, to out64. Entry hi<<8|lo is the affine
+ * point lo·G + hi·2^128·G (entry 0 is G) as x then y, each 8 little-endian
+ * 32-bit words of the canonical value. Returns -1 if first + count > 65536. */
+int kv_g_comb_fetch(kv_ctx *ctx, uint32_t first, uint32_t count, uint8_t *out64);
+
 /* ---- GPU-resident UTXO set ----
  * ⇔ UtxoCollection (consensus/core/src/utxo/utxo_collection.rs:5) + the
  * populate/diff steps (utxo_validation.rs:351-390, utxo_diff.rs:224).

@@ -199,8 +199,12 @@ extern "C" kv_ctx *kv_create(const kv_params *params) {
     unsigned long long v = strtoull(e, &end, 10);
     if (end != e && v > 0) ctx->schnorr_split_min = (size_t)v;
   }
-  /* fill the shared affine G multiples table (idempotent, once per device) */
+  /* fill the shared fixed-base tables (idempotent: every context writes the
+   * same final bytes): the two 8-bit tables on one lane, then the joint
+   * 16-bit table with one lane per entry */
   hipLaunchKernelGGL(kv::kv_ec_table_init_kernel, dim3(1), dim3(64), 0, ctx->stream);
+  hipLaunchKernelGGL(kv::kv_g_joint_init_kernel, dim3(KV_G_JOINT_ENTRIES / 256),
+                     dim3(256), 0, ctx->stream);
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
     set_error("kv_create: G-table init failed");
     delete ctx;
@@ -278,6 +282,25 @@ static int launch_schnorr_verify(kv_ctx *ctx, const uint8_t *d_tuples, size_t n,
 }
 
 extern "C" int kv_schnorr_finish_batch(void) { return KV_FINISH_K; }
+
+extern "C" int kv_g_comb_fetch(kv_ctx *ctx, uint32_t first, uint32_t count,
+                               uint8_t *out64) {
+  if (!ctx || (!out64 && count)) {
+    set_error("kv_g_comb_fetch: null argument");
+    return -1;
+  }
+  if (first > KV_G_JOINT_ENTRIES || count > KV_G_JOINT_ENTRIES - first) {
+    set_error("kv_g_comb_fetch: range exceeds the 65,536-entry table");
+    return -1;
+  }
+  if (count == 0) return 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_CHECK(hipMemcpyFromSymbolAsync(out64, HIP_SYMBOL(kv::KV_G_JOINT),
+                                     (size_t)count * 64, (size_t)first * 64,
+                                     hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
 
 static int verify_batch(kv_ctx *ctx, const uint8_t *tuples, size_t n, size_t rec_size,
                         int ecdsa, uint64_t *bitmap_out, uint8_t *status_out) {

@@ -91,18 +91,175 @@ __device__ __constant__ static const u64 GE_G_Y[4] = {
     0x9C47D08FFB10D4B8ULL, 0xFD17B448A6855419ULL, 0x5DA4FBFC0E1108A8ULL,
     0x483ADA7726A3C465ULL};
 
-/* 8-bit fixed-base table: KV_G_TABLE8[d] = d·G, d = 1..255 (entry 0 = G,
- * discarded by the digit-0 cmov). G is FIXED, so the G/φG ladder streams can
- * afford one shared 20KB L2-resident table and add every SECOND 4-bit window
- * (17 digits per 129-bit half-scalar instead of 33) — 32 fewer mixed adds
- * per verify. */
+/* 8-bit fixed-base tables: KV_G_TABLE8[d] = d·G and KV_H_TABLE8[d] = d·H with
+ * H = 2^128·G, d = 1..255 (entry 0 = the base point, never selected as a
+ * digit). They are the inputs of the joint table below; under -DKV_NO_G_JOINT
+ * the ladder's G/φG streams read KV_G_TABLE8 directly. */
 __device__ ge KV_G_TABLE8[256];
+__device__ ge KV_H_TABLE8[256];
+__device__ static fe26 KV_G8_X[256];    /* init-time scratch */
+__device__ static fe26 KV_G8_Y[256];    /* init-time scratch */
 __device__ static fe26 KV_G8_Z[256];    /* init-time scratch */
 __device__ static fe26 KV_G8_PREF[256]; /* init-time scratch */
 
+/* Joint 16-bit fixed-base table: KV_G_JOINT[hi << 8 | lo] = lo·G + hi·H.
+ * G is FIXED, so its scalar needs no GLV split: s = s_lo + 2^128·s_hi (a plain
+ * bit split), and byte j of s_lo with byte j of s_hi select ONE entry whose add
+ * lands on 4-bit window 2j — 16 mixed adds per verify where the two 8-bit
+ * G/φG streams took 34. lo == 0 or hi == 0 gives the other term alone; entry 0
+ * is G (discarded by the digit-0 cmov, but a well-formed point).
+ *
+ * An entry is the affine point as canonical 256-bit x then y, 8 little-endian
+ * u32 words each: 64 bytes, 64-byte aligned, so one entry is one half of a
+ * 128-byte line and the whole table is 4 MiB (one XCD's L2; far inside the
+ * Infinity Cache). The 80-byte ge layout would save the unpack's ~40 shifts
+ * and masks per add against 25% more lines touched and entries that straddle
+ * lines; the packed form was kept. */
+struct alignas(64) g16_entry {
+  u32 w[16];
+};
+#define KV_G_JOINT_ENTRIES 65536u
+#ifndef KV_HOST_TEST
+__device__ g16_entry KV_G_JOINT[KV_G_JOINT_ENTRIES];
+#endif
+
+/* Joint G table is the DEFAULT; -DKV_NO_G_JOINT restores the two-stream 8-bit
+ * comb (GLV-split G scalar, 34 adds) for experiments. The tables above are
+ * built either way. */
+#ifndef KV_NO_G_JOINT
+#define KV_G_JOINT_LADDER 1
+#endif
+
+/* tab[d] = d·B affine with canonical limbs, d = 1..255, tab[0] = B. One
+ * Montgomery batch inversion over all 255 Zs instead of 255 Fermat chains (the
+ * serial per-entry form cost ~35ms of every kv_create). Only FINAL values are
+ * stored to tab, so a context created while another one's kernels read the
+ * tables rewrites identical bytes. sx/sy/sz/pref: 256-entry scratch. */
+__device__ inline void g8_table_fill(ge *tab, fe26 *sx, fe26 *sy, fe26 *sz,
+                                     fe26 *pref, const ge &B) {
+  gej acc;
+  acc.x = B.x;
+  acc.y = B.y;
+  fe26_set_int(acc.z, 1);
+  for (int k = 1; k <= 255; k++) {
+    sx[k] = acc.x;
+    sy[k] = acc.y;
+    sz[k] = acc.z;
+    gej t;
+    gej_add_ge(t, acc, B);
+    acc = t;
+  }
+  pref[1] = sz[1];
+  for (int k = 2; k <= 255; k++) fe26_mul(pref[k], pref[k - 1], sz[k]);
+  fe26 inv;
+  fe26_inv(inv, pref[255]);
+  for (int k = 255; k >= 1; k--) {
+    fe26 zi;
+    if (k > 1) {
+      fe26_mul(zi, inv, pref[k - 1]);
+      fe26_mul(inv, inv, sz[k]);
+    } else {
+      zi = inv;
+    }
+    fe26 zi2, zi3;
+    ge e;
+    fe26_sqr(zi2, zi);
+    fe26_mul(zi3, zi2, zi);
+    fe26_mul(e.x, sx[k], zi2);
+    fe26_mul(e.y, sy[k], zi3);
+    fe26_normalize(e.x);
+    fe26_normalize(e.y);
+    tab[k] = e;
+  }
+  tab[0] = tab[1];
+}
+
+/* H = 2^128·G as a canonical affine point, from G by 128 doublings */
+__device__ inline void g8_h_base(ge &H, const ge &G) {
+  gej acc;
+  acc.x = G.x;
+  acc.y = G.y;
+  fe26_set_int(acc.z, 1);
+  for (int k = 0; k < 128; k++) {
+    gej t;
+    gej_double(t, acc);
+    acc = t;
+  }
+  fe26 zi, zi2, zi3;
+  fe26_inv(zi, acc.z);
+  fe26_sqr(zi2, zi);
+  fe26_mul(zi3, zi2, zi);
+  fe26_mul(H.x, acc.x, zi2);
+  fe26_mul(H.y, acc.y, zi3);
+  fe26_normalize(H.x);
+  fe26_normalize(H.y);
+}
+
+/* canonical fe26 limbs -> 8 little-endian u32 words of the 256-bit value */
+__device__ __forceinline__ void g16_pack_fe(u32 w[8], const fe26 &a) {
+  fe f;
+  fe26_to_fe(f, a);
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    w[2 * i] = (u32)f.n[i];
+    w[2 * i + 1] = (u32)(f.n[i] >> 32);
+  }
+}
+
+/* 8 little-endian u32 words of a value < p -> fe26 limbs (magnitude 1) */
+__device__ __forceinline__ void g16_unpack_fe(fe26 &r, const u32 w[8]) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    int bit = 26 * i;
+    int k = bit >> 5, sh = bit & 31;
+    u32 v = w[k] >> sh;
+    if (sh > 6 && k < 7) v |= w[k + 1] << (32 - sh);
+    r.l[i] = v & KV26_M;
+  }
+}
+
+__device__ __forceinline__ void g16_unpack(ge &e, const g16_entry &t) {
+  g16_unpack_fe(e.x, t.w);
+  g16_unpack_fe(e.y, t.w + 8);
+}
+
+/* One joint entry from the two 8-bit tables: the routine every lane of
+ * kv_g_joint_init_kernel runs, and the host build's table accessor. For lo and
+ * hi both non-zero it is one mixed add, one inversion, a normalise and a pack.
+ * lo·G and hi·H are never equal or opposite there: that needs
+ * lo ∓ hi·2^128 ≡ 0 (mod n), and 0 < |lo ∓ hi·2^128| < 2^136 < n. (The mixed
+ * add handles both cases anyway.) */
+__device__ inline void g16_build_entry(g16_entry &out, u32 idx, const ge *g8,
+                                       const ge *h8) {
+  u32 lo = idx & 255, hi = (idx >> 8) & 255;
+  ge e;
+  if (hi == 0) {
+    e = g8[lo]; /* lo == 0: g8[0] = G */
+  } else if (lo == 0) {
+    e = h8[hi];
+  } else {
+    gej a, s;
+    a.x = g8[lo].x;
+    a.y = g8[lo].y;
+    fe26_set_int(a.z, 1);
+    gej_add_ge(s, a, h8[hi]);
+    fe26 zi, zi2, zi3;
+    fe26_inv(zi, s.z);
+    fe26_sqr(zi2, zi);
+    fe26_mul(zi3, zi2, zi);
+    fe26_mul(e.x, s.x, zi2);
+    fe26_mul(e.y, s.y, zi3);
+    fe26_normalize(e.x);
+    fe26_normalize(e.y);
+  }
+  g16_pack_fe(out.w, e.x);
+  g16_pack_fe(out.w + 8, e.y);
+}
+
+/* Table init, phase one (single lane): the two 8-bit tables. */
 extern "C" __global__ void kv_ec_table_init_kernel() {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  ge G;
+  ge G, H;
   {
     fe gx, gy;
 #pragma unroll
@@ -113,43 +270,49 @@ extern "C" __global__ void kv_ec_table_init_kernel() {
     fe26_from_fe(G.x, gx);
     fe26_from_fe(G.y, gy);
   }
-  /* one Montgomery batch inversion over all 255 Zs instead of 255 Fermat
-   * chains (the serial per-entry form cost ~35ms of every kv_create) */
-  gej acc;
-  acc.x = G.x;
-  acc.y = G.y;
-  fe26_set_int(acc.z, 1);
-  KV_G_TABLE8[0] = G;
-  for (int k = 1; k <= 255; k++) {
-    KV_G_TABLE8[k].x = acc.x;
-    KV_G_TABLE8[k].y = acc.y;
-    KV_G8_Z[k] = acc.z;
-    gej t;
-    gej_add_ge(t, acc, G);
-    acc = t;
-  }
-  KV_G8_PREF[1] = KV_G8_Z[1];
-  for (int k = 2; k <= 255; k++)
-    fe26_mul(KV_G8_PREF[k], KV_G8_PREF[k - 1], KV_G8_Z[k]);
-  fe26 inv;
-  fe26_inv(inv, KV_G8_PREF[255]);
-  for (int k = 255; k >= 1; k--) {
-    fe26 zi;
-    if (k > 1) {
-      fe26_mul(zi, inv, KV_G8_PREF[k - 1]);
-      fe26_mul(inv, inv, KV_G8_Z[k]);
-    } else {
-      zi = inv;
-    }
-    fe26 zi2, zi3;
-    fe26_sqr(zi2, zi);
-    fe26_mul(zi3, zi2, zi);
-    fe26_mul(KV_G_TABLE8[k].x, KV_G_TABLE8[k].x, zi2);
-    fe26_mul(KV_G_TABLE8[k].y, KV_G_TABLE8[k].y, zi3);
-    fe26_normalize(KV_G_TABLE8[k].x);
-    fe26_normalize(KV_G_TABLE8[k].y);
-  }
+  g8_table_fill(KV_G_TABLE8, KV_G8_X, KV_G8_Y, KV_G8_Z, KV_G8_PREF, G);
+  g8_h_base(H, G);
+  g8_table_fill(KV_H_TABLE8, KV_G8_X, KV_G8_Y, KV_G8_Z, KV_G8_PREF, H);
 }
+
+#ifndef KV_HOST_TEST
+/* Table init, phase two: one lane per joint entry (grid covers exactly
+ * KV_G_JOINT_ENTRIES lanes; the guard keeps any other launch in bounds). */
+extern "C" __global__ void __launch_bounds__(256) kv_g_joint_init_kernel() {
+  u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= KV_G_JOINT_ENTRIES) return;
+  g16_entry e;
+  g16_build_entry(e, idx, KV_G_TABLE8, KV_H_TABLE8);
+  KV_G_JOINT[idx] = e;
+}
+
+__device__ __forceinline__ void g16_fetch(ge &e, u32 idx) {
+  g16_unpack(e, KV_G_JOINT[idx & (KV_G_JOINT_ENTRIES - 1)]);
+}
+#else
+/* Host build: the shims fill KV_G_TABLE8 only, so the accessor builds the H
+ * multiples from it (again whenever its base entry changed) and computes the
+ * requested entry on demand with the init kernel's per-entry routine. */
+static inline void g16_fetch(ge &e, u32 idx) {
+  static ge base;
+  static bool have = false;
+  static fe26 sx[256], sy[256], sz[256], pref[256];
+  bool same = have;
+  for (int i = 0; same && i < 10; i++)
+    same = base.x.l[i] == KV_G_TABLE8[1].x.l[i] &&
+           base.y.l[i] == KV_G_TABLE8[1].y.l[i];
+  if (!same) {
+    ge H;
+    base = KV_G_TABLE8[1];
+    g8_h_base(H, base);
+    g8_table_fill(KV_H_TABLE8, sx, sy, sz, pref, H);
+    have = true;
+  }
+  g16_entry t;
+  g16_build_entry(t, idx & (KV_G_JOINT_ENTRIES - 1), KV_G_TABLE8, KV_H_TABLE8);
+  g16_unpack(e, t);
+}
+#endif
 
 /* ---------------- GLV endomorphism scalar decomposition ----------------
  * secp256k1 has an efficient endomorphism φ(x,y) = (β·x, y) with φ(P) = λ·P.
@@ -315,8 +478,22 @@ struct ladder_consts {
   fe26 beta; /* GLV β */
   fe26 zg2;  /* Zg² */
   fe26 zg3;  /* Zg³ */
+#ifndef KV_G_JOINT_LADDER
   fe26 bzg2; /* β·Zg² */
+#endif
 };
+
+/* The G digits of one even ladder window, as the frames pass them along: the
+ * joint table's 16-bit index, or the two 8-bit comb digits with their signs. */
+#ifdef KV_G_JOINT_LADDER
+struct g_digits {
+  u32 idx;
+};
+#else
+struct g_digits {
+  u64 d1, n1, d2, n2;
+};
+#endif
 
 /* Per-lane P table without an inversion. The chain acc_k = acc_{k-1} + P has
  * Z_k = Z_{k-1}·zr_k, so with Zg = Z_max and m_k = ∏_{j>k} zr_j = Zg/Z_k the
@@ -366,13 +543,16 @@ template <bool IS_G, bool PHI>
 __device__ __forceinline__ void ladder_entry(ge &e, const ge &tab,
                                              const ladder_consts &lc, u64 neg) {
   e = tab;
+#ifndef KV_G_JOINT_LADDER
   if (IS_G) { /* one multiply per coordinate: φ's β rides on Zg² */
     fe26 mx, my;
     fe26_mul(mx, e.x, PHI ? lc.bzg2 : lc.zg2);
     fe26_mul(my, e.y, lc.zg3);
     e.x = mx;
     e.y = my;
-  } else if (PHI) {
+  } else
+#endif
+  if (PHI) {
     fe26 bx;
     fe26_mul(bx, e.x, lc.beta);
     e.x = bx;
@@ -393,18 +573,36 @@ __device__ __forceinline__ void ladder_add(gej &R, const ge &tab,
   gej_cmov(R, t, (u64)(digit != 0));
 }
 
-/* One full ladder window in ONE call frame: 4 doublings + the 4 stream adds
- * (G, φG, P, φP). The group ops inline INSIDE this body, so the accumulator
- * crosses the noinline ABI once per window instead of five times — the r02
- * PMC showed the per-call scratch spills of R/temps were the kernel's
- * dominant memory traffic (~119KB/verify). Full kernel-wide inlining is not
- * an option: it reproducibly hangs gfx950 (measured again this round); this
- * bounded body (~5k instructions) stays under that cliff. */
-template <bool DOUBLE>
+/* the G adds of one even window */
+__device__ __forceinline__ void ladder_add_g(gej &R, const ladder_consts &lc,
+                                             const g_digits &g) {
+#ifdef KV_G_JOINT_LADDER
+  /* one add of lo·G + hi·H: a 64-byte gather, the unpack (magnitude 1) and
+   * the map onto the ladder's curve; no sign and no β apply */
+  ge e, m;
+  gej t;
+  g16_fetch(e, g.idx);
+  fe26_mul(m.x, e.x, lc.zg2);
+  fe26_mul(m.y, e.y, lc.zg3);
+  gej_add_ge_impl(t, R, m);
+  gej_cmov(R, t, (u64)(g.idx != 0));
+#else
+  ladder_add<true, false>(R, KV_G_TABLE8[g.d1], lc, g.d1, g.n1); /* G (8-bit) */
+  ladder_add<true, true>(R, KV_G_TABLE8[g.d2], lc, g.d2, g.n2);  /* φG */
+#endif
+}
+
+/* One full ladder window in ONE call frame: 4 doublings + the stream adds
+ * (G on even windows, then P, φP). The group ops inline INSIDE this body, so
+ * the accumulator crosses the noinline ABI once per window instead of once per
+ * group op — the r02 PMC showed the per-call scratch spills of R/temps were
+ * the kernel's dominant memory traffic (~119KB/verify). Full kernel-wide
+ * inlining is not an option: it reproducibly hangs gfx950 (measured again this
+ * round); this bounded body (~5k instructions) stays under that cliff. */
+template <bool DOUBLE, bool G_ACTIVE>
 __device__ __forceinline__ void gej_window_impl(gej &R, const ge *ptab,
                                                 const ladder_consts &lc,
-                                                u64 g_active, u64 dg1, u64 ng1,
-                                                u64 dg2, u64 ng2, u64 dp1,
+                                                const g_digits &g, u64 dp1,
                                                 u64 np1, u64 dp2, u64 np2) {
   if (DOUBLE) {
     gej t;
@@ -413,34 +611,38 @@ __device__ __forceinline__ void gej_window_impl(gej &R, const ge *ptab,
     gej_double_impl(t, R);
     gej_double_impl(R, t);
   }
-  if (g_active) { /* wave-uniform: G adds land on every second window */
-    ladder_add<true, false>(R, KV_G_TABLE8[dg1], lc, dg1, ng1); /* G (8-bit) */
-    ladder_add<true, true>(R, KV_G_TABLE8[dg2], lc, dg2, ng2);  /* φG */
-  }
+  if (G_ACTIVE) ladder_add_g(R, lc, g); /* G adds land on every second window */
   ladder_add<false, false>(R, ptab[dp1], lc, dp1, np1); /* P */
   ladder_add<false, true>(R, ptab[dp2], lc, dp2, np2);  /* φP */
 }
 
 __device__ KV_GROUP_ATTR void gej_window_step(gej &R, const ge *ptab,
                                               const ladder_consts &lc,
-                                              u64 g_active, u64 dg1, u64 ng1,
-                                              u64 dg2, u64 ng2, u64 dp1, u64 np1,
-                                              u64 dp2, u64 np2) {
-  gej_window_impl<true>(R, ptab, lc, g_active, dg1, ng1, dg2, ng2, dp1, np1,
-                        dp2, np2);
+                                              u64 g_active, g_digits g, u64 dp1,
+                                              u64 np1, u64 dp2, u64 np2) {
+  if (g_active) /* wave-uniform */
+    gej_window_impl<true, true>(R, ptab, lc, g, dp1, np1, dp2, np2);
+  else
+    gej_window_impl<true, false>(R, ptab, lc, g, dp1, np1, dp2, np2);
 }
 
 /* The ladder's top window: R starts at infinity, so its four doublings would
  * double infinity. This frame sets R and runs the window's adds only (all
- * digits zero leaves R at infinity). */
+ * digits zero leaves R at infinity). With the joint table the G scalar's
+ * halves are exactly 128 bits and window 32 carries P digits alone. */
 __device__ KV_GROUP_ATTR void gej_window_first(gej &R, const ge *ptab,
-                                               const ladder_consts &lc, u64 dg1,
-                                               u64 ng1, u64 dg2, u64 ng2,
+                                               const ladder_consts &lc,
+#ifndef KV_G_JOINT_LADDER
+                                               g_digits g,
+#endif
                                                u64 dp1, u64 np1, u64 dp2,
                                                u64 np2) {
   gej_set_infinity(R);
-  gej_window_impl<false>(R, ptab, lc, 1, dg1, ng1, dg2, ng2, dp1, np1, dp2,
-                         np2);
+#ifdef KV_G_JOINT_LADDER
+  gej_window_impl<false, false>(R, ptab, lc, g_digits{0}, dp1, np1, dp2, np2);
+#else
+  gej_window_impl<false, true>(R, ptab, lc, g, dp1, np1, dp2, np2);
+#endif
 }
 
 /* Pair-window frames are the DEFAULT (measured 41.1M vs 39.6M verifies/s);
@@ -451,50 +653,57 @@ __device__ KV_GROUP_ATTR void gej_window_first(gej &R, const ge *ptab,
 
 #ifdef KV_PAIR_WINDOWS
 /* Two ladder windows per call frame: 8 doublings + both windows' stream adds
- * (G digits are 8-bit and land only on the even window). Halves the
- * accumulator's ABI crossings (17 frames vs 33) at the cost of a ~2x body —
- * under the gfx950 long-body hang cliff (full inlining still hangs). */
+ * (the G add lands only on the even window: 5 adds with the joint table).
+ * Halves the accumulator's ABI crossings (17 frames vs 33) at the cost of a
+ * ~2x body — under the gfx950 long-body hang cliff (full inlining still
+ * hangs). */
 __device__ __forceinline__ void gej_window_pair_impl(
-    gej &R, const ge *ptab, const ladder_consts &lc, u64 dg1, u64 ng1, u64 dg2,
-    u64 ng2, u64 hp1, u64 hn1, u64 hp2, u64 hn2, /* odd-window P digits + negs */
+    gej &R, const ge *ptab, const ladder_consts &lc, const g_digits &g,
+    u64 hp1, u64 hn1, u64 hp2, u64 hn2, /* odd-window P digits + negs */
     u64 lp1, u64 ln1, u64 lp2, u64 ln2 /* even-window P digits + negs */) {
   /* odd window: P streams only */
-  gej_window_impl<true>(R, ptab, lc, 0, 0, 0, 0, 0, hp1, hn1, hp2, hn2);
-  /* even window: G comb + P streams */
-  gej_window_impl<true>(R, ptab, lc, 1, dg1, ng1, dg2, ng2, lp1, ln1, lp2, ln2);
+  gej_window_impl<true, false>(R, ptab, lc, g, hp1, hn1, hp2, hn2);
+  /* even window: G + P streams */
+  gej_window_impl<true, true>(R, ptab, lc, g, lp1, ln1, lp2, ln2);
 }
 
 __device__ KV_GROUP_ATTR void gej_window_step2(gej &R, const ge *ptab,
-                                               const ladder_consts &lc, u64 dg1,
-                                               u64 ng1, u64 dg2, u64 ng2,
-                                               u64 hp1, u64 hn1, u64 hp2,
-                                               u64 hn2, u64 lp1, u64 ln1,
-                                               u64 lp2, u64 ln2) {
-  gej_window_pair_impl(R, ptab, lc, dg1, ng1, dg2, ng2, hp1, hn1, hp2, hn2,
-                       lp1, ln1, lp2, ln2);
+                                               const ladder_consts &lc,
+                                               g_digits g, u64 hp1, u64 hn1,
+                                               u64 hp2, u64 hn2, u64 lp1,
+                                               u64 ln1, u64 lp2, u64 ln2) {
+  gej_window_pair_impl(R, ptab, lc, g, hp1, hn1, hp2, hn2, lp1, ln1, lp2, ln2);
 }
 
 #ifdef KV_QUAD_WINDOWS
 /* four windows (two pairs) per frame: 9 frames per ladder */
 __device__ KV_GROUP_ATTR void gej_window_step4(gej &R, const ge *ptab,
                                                const ladder_consts &lc,
-                                               const u64 a[12], const u64 b[12]) {
-  gej_window_pair_impl(R, ptab, lc, a[0], a[1], a[2], a[3], a[4], a[5], a[6],
-                       a[7], a[8], a[9], a[10], a[11]);
-  gej_window_pair_impl(R, ptab, lc, b[0], b[1], b[2], b[3], b[4], b[5], b[6],
-                       b[7], b[8], b[9], b[10], b[11]);
+                                               g_digits ga, g_digits gb,
+                                               const u64 a[8], const u64 b[8]) {
+  gej_window_pair_impl(R, ptab, lc, ga, a[0], a[1], a[2], a[3], a[4], a[5],
+                       a[6], a[7]);
+  gej_window_pair_impl(R, ptab, lc, gb, b[0], b[1], b[2], b[3], b[4], b[5],
+                       b[6], b[7]);
 }
 #endif
 #endif
 
-/* R = gs·G + ps·P via GLV-split 4-bit windows: 33 window steps (the top one
- * without doublings, R being infinity there) of 4 doublings + 4 selected adds (G, φG, P, φP streams; φ applied at add time as one β·x
- * field multiply; negative half-scalars negate the added point's y). */
+/* R = gs·G + ps·P. ps is GLV-split into two signed 129-bit halves read as
+ * 4-bit windows: 33 window steps (the top one without doublings, R being
+ * infinity there) of 4 doublings + the P and φP adds (φ applied at add time as
+ * one β·x field multiply; negative half-scalars negate the added point's y).
+ * gs is split at bit 128 and adds one joint-table entry on every second
+ * window (see KV_G_JOINT); under KV_NO_G_JOINT it is GLV-split too and feeds
+ * two 8-bit comb streams, G and φG. */
 __device__ inline void ecmult_double(gej &R, const sc &gs, const sc &ps,
                                      const ge &P) {
-  glv_half g1h, g2h, p1h, p2h;
-  glv_split(gs, g1h, g2h);
+  glv_half p1h, p2h;
   glv_split(ps, p1h, p2h);
+#ifndef KV_G_JOINT_LADDER
+  glv_half g1h, g2h;
+  glv_split(gs, g1h, g2h);
+#endif
   /* Per-lane P table, affine over the common denominator Zg (80B entries:
    * the working set fits MALL and the P streams are MIXED adds, 11 vs 16
    * fe_muls). The ladder runs on the isomorphic curve where these entries
@@ -513,7 +722,9 @@ __device__ inline void ecmult_double(gej &R, const sc &gs, const sc &ps,
 #pragma unroll
     for (int i = 0; i < 4; i++) bu.n[i] = GLV_BETA[i];
     fe26_from_fe(lc.beta, bu);
+#ifndef KV_G_JOINT_LADDER
     fe26_mul(lc.bzg2, lc.beta, lc.zg2);
+#endif
   }
   /* per-stream digit/neg accessors: unsigned fixed windows by default,
    * signed fixed windows (8-entry table) under KV_SIGNED_PTAB */
@@ -528,43 +739,49 @@ __device__ inline void ecmult_double(gej &R, const sc &gs, const sc &ps,
 #define KV_DP2(w) glv_digit(p2h, w)
 #define KV_DN2(w) (p2h.neg)
 #endif
-  /* window 32 alone: the G digit sits at even position 32, and R starts at
-   * infinity, so this frame has adds only */
-  gej_window_first(R, ptab, lc, glv_digit8(g1h, 32), g1h.neg,
-                   glv_digit8(g2h, 32), g2h.neg, KV_DP1(32), KV_DN1(32),
-                   KV_DP2(32), KV_DN2(32));
+  /* G digits of even window w */
+#ifdef KV_G_JOINT_LADDER
+  /* byte w/2 of the high half over byte w/2 of the low half */
+#define KV_GD(w)                                                               \
+  (g_digits{(u32)((gs.d[2 + ((w) >> 4)] >> (((w) & 14) << 2)) & 255) << 8 |    \
+            (u32)((gs.d[(w) >> 4] >> (((w) & 14) << 2)) & 255)})
+#else
+#define KV_GD(w)                                                               \
+  (g_digits{glv_digit8(g1h, w), g1h.neg, glv_digit8(g2h, w), g2h.neg})
+#endif
+  /* window 32 alone: R starts at infinity, so this frame has adds only */
+  gej_window_first(R, ptab, lc,
+#ifndef KV_G_JOINT_LADDER
+                   KV_GD(32),
+#endif
+                   KV_DP1(32), KV_DN1(32), KV_DP2(32), KV_DN2(32));
 #if defined(KV_QUAD_WINDOWS)
   /* 8 quad frames (two pairs each) */
 #pragma unroll 1
   for (int w = 31; w >= 3; w -= 4) {
-    u64 a[12] = {glv_digit8(g1h, w - 1), g1h.neg, glv_digit8(g2h, w - 1),
-                 g2h.neg, KV_DP1(w), KV_DN1(w), KV_DP2(w), KV_DN2(w),
-                 KV_DP1(w - 1), KV_DN1(w - 1), KV_DP2(w - 1), KV_DN2(w - 1)};
-    u64 b[12] = {glv_digit8(g1h, w - 3), g1h.neg, glv_digit8(g2h, w - 3),
-                 g2h.neg, KV_DP1(w - 2), KV_DN1(w - 2), KV_DP2(w - 2), KV_DN2(w - 2),
-                 KV_DP1(w - 3), KV_DN1(w - 3), KV_DP2(w - 3), KV_DN2(w - 3)};
-    gej_window_step4(R, ptab, lc, a, b);
+    u64 a[8] = {KV_DP1(w), KV_DN1(w), KV_DP2(w), KV_DN2(w),
+                KV_DP1(w - 1), KV_DN1(w - 1), KV_DP2(w - 1), KV_DN2(w - 1)};
+    u64 b[8] = {KV_DP1(w - 2), KV_DN1(w - 2), KV_DP2(w - 2), KV_DN2(w - 2),
+                KV_DP1(w - 3), KV_DN1(w - 3), KV_DP2(w - 3), KV_DN2(w - 3)};
+    gej_window_step4(R, ptab, lc, KV_GD(w - 1), KV_GD(w - 3), a, b);
   }
 #elif defined(KV_PAIR_WINDOWS)
   /* 16 window pairs */
 #pragma unroll 1
   for (int w = 31; w >= 1; w -= 2) {
-    gej_window_step2(R, ptab, lc,
-                     glv_digit8(g1h, w - 1), g1h.neg,
-                     glv_digit8(g2h, w - 1), g2h.neg,
+    gej_window_step2(R, ptab, lc, KV_GD(w - 1),
                      KV_DP1(w), KV_DN1(w), KV_DP2(w), KV_DN2(w),
                      KV_DP1(w - 1), KV_DN1(w - 1), KV_DP2(w - 1), KV_DN2(w - 1));
   }
 #else
 #pragma unroll 1
   for (int w = 31; w >= 0; w--) {
-    u64 g_active = (w & 1) == 0; /* 8-bit G digits at even window positions */
-    gej_window_step(R, ptab, lc, g_active,
-                    g_active ? glv_digit8(g1h, w) : 0, g1h.neg,
-                    g_active ? glv_digit8(g2h, w) : 0, g2h.neg,
+    u64 g_active = (w & 1) == 0; /* G digits sit at even window positions */
+    gej_window_step(R, ptab, lc, g_active, KV_GD(w & ~1),
                     KV_DP1(w), KV_DN1(w), KV_DP2(w), KV_DN2(w));
   }
 #endif
+#undef KV_GD
 #undef KV_DP1
 #undef KV_DN1
 #undef KV_DP2

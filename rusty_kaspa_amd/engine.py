@@ -93,6 +93,15 @@ class Engine:
         self._check(rc)
         return (list(bitmap), bytes(status) if with_status else None)
 
+    def g_comb_fetch(self, first: int, count: int) -> bytes:
+        """`count` 64-byte entries of the joint fixed-base table from `first`."""
+        out = (ctypes.c_uint8 * (64 * count))()
+        rc = self.lib.kv_g_comb_fetch(ctypes.c_void_p(self.ctx),
+                                      ctypes.c_uint32(first),
+                                      ctypes.c_uint32(count), out)
+        self._check(rc)
+        return bytes(out)
+
     def muhash_finalize(self, partial768: bytes) -> bytes:
         out = (ctypes.c_uint8 * 32)()
         rc = self.lib.kv_muhash_finalize(ctypes.c_void_p(self.ctx), partial768, out)
