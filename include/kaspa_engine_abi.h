@@ -245,8 +245,9 @@ int kv_g_comb_fetch(kv_ctx *ctx, uint32_t first, uint32_t count, uint8_t *out64)
  * a device-side ARENA: the entry carries flags bit1
  * (KV_UTXO_F_SPK_ARENA) and its spk field's first 4 bytes are the u32 arena
  * byte offset. Arena space is bump-allocated; removing an entry leaks its
- * arena span until the next kv_utxo_reset (documented trade: non-standard
- * outputs are rare and the arena compacts on reset). */
+ * arena span until the next kv_utxo_reset or kv_utxo_rehash (documented trade:
+ * non-standard outputs are rare; the arena compacts on reset and on rehash,
+ * and kv_utxo_stats reports the leaked bytes). */
 #define KV_UTXO_F_COINBASE 1u
 #define KV_UTXO_F_SPK_ARENA 2u
 #define KV_UTXO_MAX_SPK 10000u
@@ -326,6 +327,93 @@ int kv_utxo_commitment_window(void); /* slots per scan window, as compiled */
 int kv_utxo_import_chunk(kv_ctx *ctx, const uint8_t *outpoints, const uint8_t *entries64,
                          const uint8_t *spk_blob, size_t spk_blob_len, size_t n,
                          uint8_t acc_partial768[768] /* in/out */);
+
+/* ---- UTXO table maintenance: stats, rehash, export ----
+ * The table's capacity is fixed at kv_utxo_reset, removes leave tombstones
+ * that only an upsert probing through them reuses, and the arena only grows.
+ * These three calls let a host watch that and repair it without losing the
+ * set. Nothing is automatic: kv_utxo_upsert still returns -3 on a full table,
+ * and the host decides when to rehash. */
+
+typedef struct kv_utxo_table_stats {
+  uint64_t slots;            /* slot count (power of two), 0 if never reset */
+  uint64_t n_live, n_tomb, n_empty; /* sum == slots */
+  uint64_t arena_used;       /* bump head, bytes */
+  uint64_t arena_live_bytes; /* sum of spk_len over READY entries with KV_UTXO_F_SPK_ARENA */
+  uint64_t arena_cap;
+} kv_utxo_table_stats;
+
+/* One pass over the slot array: slot states are counted per wave by ballot +
+ * popcount, arena bytes by a wave reduction, one atomic per wave per counter;
+ * one 40 B record is copied back after one stream synchronisation. Read-only,
+ * takes the context lock, stream-ordered after earlier mutations. A
+ * never-reset context gives all zeros and returns 0. arena_used -
+ * arena_live_bytes is the arena garbage a kv_utxo_rehash would reclaim; lookup,
+ * remove and upsert probe until the first EMPTY slot, so a falling n_empty is
+ * the signal that probe chains are growing. */
+int kv_utxo_stats(kv_ctx *ctx, kv_utxo_table_stats *out);
+
+/* Rebuild the set into a fresh table and a fresh arena: grows a full table,
+ * shrinks a sparse one, and compacts tombstones and arena garbage.
+ * capacity means what it means for kv_utxo_reset (entries; slots = smallest
+ * power of two >= max(64, 2*capacity)); capacity == 0 keeps the current slot
+ * count, a pure compaction. If the resulting slot count is < 2*n_live the call
+ * fails, except for capacity == 0, which keeps whatever load the table has.
+ *  - Device chain, all on the context's stream: the kv_utxo_stats pass gives
+ *    n_live and arena_live_bytes, from which the new table and arena are
+ *    allocated (arena: 1 MiB doubled until it holds arena_live_bytes, the
+ *    rounding of the growing arena). Then, per window of
+ *    kv_utxo_commitment_window() source slots, the commitment's compaction
+ *    kernel packs the READY slot indices and an insert kernel places each in
+ *    the new table, reading the window's live count from device memory — no
+ *    per-window host round trip. Long scripts are re-allocated back to back in
+ *    the new arena by a 64-bit device cursor and moved by a block-per-script
+ *    copy kernel. One record (inserted count, new arena head, status) is
+ *    copied back after one synchronisation.
+ *  - Atomic: the table, its capacity, the arena, its capacity and its head are
+ *    swapped only after the device work has completed and reported no failure,
+ *    and the old allocations are freed after the swap. On ANY error the old
+ *    table and arena are still in place and unchanged.
+ *  - Transient device memory is therefore old + new: both tables (112 B per
+ *    slot) and both arenas are alive until the swap.
+ * After a successful call n_tomb == 0, n_live is unchanged, arena_used ==
+ * arena_live_bytes, every entry is retrievable with identical bytes and
+ * kv_utxo_commitment is unchanged mod P.
+ * kernel_ms is hipEvent time over the stats pass plus the rebuild chain.
+ * Returns -1 never reset, -2 allocation failure, -3 capacity too small for the
+ * live set, a READY entry whose script reference is out of range, or a
+ * compacted arena beyond what a u32 offset addresses. */
+int kv_utxo_rehash(kv_ctx *ctx, uint64_t capacity, double *kernel_ms /*optional*/);
+
+/* ⇔ get_pruning_point_utxos / get_virtual_utxos (consensus/src/consensus/
+ *   mod.rs:1067-1108, seek_iterator(from_outpoint, chunk_size, skip_first)):
+ *   the serving half of pruning-point sync, of which kv_utxo_import_chunk is
+ *   the receiving half. A slot cursor stands in for from_outpoint +
+ *   skip_first.
+ * Walk: start with *cursor = 0 and call until *cursor == stats.slots with
+ * *n_out == 0. Entries come out in ascending slot order and *cursor is
+ * advanced to one past the last slot consumed; a full walk with no mutation in
+ * between yields every live entry exactly once. The reference iterates in DB
+ * key order; order carries no consensus meaning here, because the receiver
+ * folds a commutative multiset (kv_utxo_import_chunk).
+ * Output is exactly the input format of kv_utxo_upsert_spk /
+ * kv_utxo_import_chunk, so a chunk can be fed straight back: inline entries
+ * are copied as stored; an arena entry has KV_UTXO_F_SPK_ARENA cleared and its
+ * 36-byte spk field zeroed, and its script bytes are appended to spk_out in
+ * entry order (*spk_used = total).
+ * spk_cap must be >= KV_UTXO_MAX_SPK (else -1), so one entry always fits. A
+ * chunk ends early, with the cursor before the next entry, when that entry's
+ * script would not fit; it may also come back short of max_entries — empty
+ * even — at the end of the span of slots one call scans (sized from
+ * max_entries, at most one commitment window and never across a window
+ * boundary). Callers loop until the end condition.
+ * Read-only on the table, under the context lock. Returns -3 if an entry's
+ * script reference lies outside the arena. */
+int kv_utxo_export_chunk(kv_ctx *ctx, uint64_t *cursor /* in/out, slot index; start at 0 */,
+                         size_t max_entries,
+                         uint8_t *outpoints_out /*[36*max]*/, uint8_t *entries_out /*[64*max]*/,
+                         uint8_t *spk_out, size_t spk_cap, size_t *spk_used,
+                         size_t *n_out);
 
 /* Populate + validate + (optionally) apply the UTXO diff — the full virtual
  * processor step for one block (utxo_validation.rs:351-390 populate, then

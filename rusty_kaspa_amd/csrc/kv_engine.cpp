@@ -12,6 +12,7 @@
 #include "kv_u3072.h"
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <mutex>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,6 +28,7 @@
 #include "kv_sighash_kernels.hip"
 #include "kv_utxo_kernels.hip"
 #include "kv_utxo_commit_kernels.hip"
+#include "kv_utxo_rehash_kernels.hip"
 #include "kv_validate_host.inc"
 #include "kv_script_host.inc"
 
@@ -148,6 +150,12 @@ struct kv_ctx {
   uint8_t *d_cm_fixed = nullptr;
   uint64_t *d_cm_elems = nullptr;
   size_t d_cm_elems_cap = 0;
+  /* table maintenance (kv_utxo_rehash_kernels.hip): the two small copy-back
+   * records of kv_utxo_stats / kv_utxo_rehash, and the export walk's per-entry
+   * script references */
+  uint8_t *d_tbl_rec = nullptr;
+  unsigned long long *d_exp_refs = nullptr;
+  size_t d_exp_refs_cap = 0;
   /* split Schnorr verify (launch_schnorr_verify): the ladder kernel's R limbs
    * and pre-status, 121 B per signature. Written and read on ctx->stream only,
    * under ctx->mu. */
@@ -245,6 +253,8 @@ extern "C" void kv_destroy(kv_ctx *ctx) {
   if (ctx->d_sfin) (void)hipFree(ctx->d_sfin);
   if (ctx->d_cm_fixed) (void)hipFree(ctx->d_cm_fixed);
   if (ctx->d_cm_elems) (void)hipFree(ctx->d_cm_elems);
+  if (ctx->d_tbl_rec) (void)hipFree(ctx->d_tbl_rec);
+  if (ctx->d_exp_refs) (void)hipFree(ctx->d_exp_refs);
   (void)hipGetLastError(); /* teardown calls are fire-and-forget; do not leave
       their errors sticky for the next engine's launch checks (a swallowed
       invalid-argument here surfaced as a spurious failure in the NEXT
@@ -1902,7 +1912,8 @@ static int arena_reserve(kv_ctx *ctx, uint64_t need) {
 }
 
 /* general upsert: spk_len > 36 entries spill their scripts to the arena
- * (bump-allocated; spans leak on remove until kv_utxo_reset — documented) */
+ * (bump-allocated; spans leak on remove until kv_utxo_reset or kv_utxo_rehash
+ * — documented) */
 static int utxo_upsert_spk_nolock(kv_ctx *ctx, const uint8_t *outpoints,
                                   const uint8_t *entries64, const uint8_t *spk_blob,
                                   size_t spk_blob_len, size_t n) {
@@ -2313,6 +2324,357 @@ extern "C" int kv_utxo_import_chunk(kv_ctx *ctx, const uint8_t *outpoints,
   memcpy(an.l, acc_partial768, 384);
   kv::u3072_mulmod(r, an, prod);
   memcpy(acc_partial768, r.l, 384);
+  return 0;
+}
+
+/* ---------------- table maintenance (kv_utxo_rehash_kernels.hip) -------------
+ * stats, rehash / grow / shrink / compaction, and the export walk ⇔
+ * get_pruning_point_utxos / get_virtual_utxos (consensus/mod.rs:1067-1108). */
+
+namespace {
+constexpr size_t TR_OFF_SCAN = 0;    /* kv::table_scan_rec */
+constexpr size_t TR_OFF_REHASH = 64; /* kv::rehash_rec */
+constexpr size_t TR_BYTES = 128;
+static_assert(sizeof(kv::table_scan_rec) <= TR_OFF_REHASH &&
+                  TR_OFF_REHASH + sizeof(kv::rehash_rec) <= TR_BYTES,
+              "table records outgrew their pads");
+} // namespace
+
+/* the stats pass on ctx->stream: one kernel, one 40 B record back, one
+ * synchronisation. Needs a table. */
+static int utxo_scan_nolock(kv_ctx *ctx, kv::table_scan_rec *h_rec, float *ms) {
+  if (!ctx->d_tbl_rec) {
+    if (hipMalloc(&ctx->d_tbl_rec, TR_BYTES) != hipSuccess) {
+      ctx->d_tbl_rec = nullptr;
+      set_error("kv_utxo table records: hipMalloc failed");
+      return -2;
+    }
+  }
+  kv::table_scan_rec *d_rec = (kv::table_scan_rec *)(ctx->d_tbl_rec + TR_OFF_SCAN);
+  uint32_t blocks = (uint32_t)std::min<uint64_t>((ctx->utxo_cap + 255) / 256,
+                                                 KV_STATS_MAX_BLOCKS);
+  hipEvent_t t0, t1;
+  HIP_CHECK(hipEventCreate(&t0));
+  if (hipEventCreate(&t1) != hipSuccess) {
+    (void)hipEventDestroy(t0);
+    set_error("kv_utxo_stats: hipEventCreate failed");
+    return -2;
+  }
+  hipError_t e = hipEventRecord(t0, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(d_rec, 0, sizeof(kv::table_scan_rec), ctx->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(kv::kv_utxo_stats_kernel, dim3(blocks), dim3(256), 0,
+                       ctx->stream, (const kv::utxo_slot *)ctx->d_utxo,
+                       ctx->utxo_cap, d_rec);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(t1, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(h_rec, d_rec, sizeof(kv::table_scan_rec),
+                       hipMemcpyDeviceToHost, ctx->stream);
+  hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  if (ms) {
+    *ms = 0.f;
+    if (e == hipSuccess && e2 == hipSuccess) (void)hipEventElapsedTime(ms, t0, t1);
+  }
+  (void)hipEventDestroy(t0);
+  (void)hipEventDestroy(t1);
+  HIP_CHECK(e);
+  HIP_CHECK(e2);
+  return 0;
+}
+
+extern "C" int kv_utxo_stats(kv_ctx *ctx, kv_utxo_table_stats *out) {
+  if (!ctx || !out) {
+    set_error("kv_utxo_stats: null argument");
+    return -1;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  (void)hipGetLastError(); /* clear any stale per-thread error so the
+      launch-config checks below only see THIS call's launches */
+  memset(out, 0, sizeof(*out));
+  if (!ctx->d_utxo) return 0; /* never reset */
+  kv::table_scan_rec rec;
+  int rc = utxo_scan_nolock(ctx, &rec, nullptr);
+  if (rc) return rc;
+  out->slots = ctx->utxo_cap;
+  out->n_live = rec.n_live;
+  out->n_tomb = rec.n_tomb;
+  out->n_empty = rec.n_empty;
+  out->arena_used = ctx->arena_head;
+  out->arena_live_bytes = rec.arena_live_bytes;
+  out->arena_cap = ctx->arena_cap;
+  return 0;
+}
+
+extern "C" int kv_utxo_rehash(kv_ctx *ctx, uint64_t capacity, double *kernel_ms) {
+  if (!ctx) {
+    set_error("kv_utxo_rehash: null ctx");
+    return -1;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  (void)hipGetLastError(); /* clear any stale per-thread error so the
+      launch-config checks below only see THIS call's launches */
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (!ctx->d_utxo) {
+    set_error("kv_utxo_rehash: call kv_utxo_reset first");
+    return -1;
+  }
+  kv::table_scan_rec scan;
+  float scan_ms = 0.f;
+  int rc = utxo_scan_nolock(ctx, &scan, &scan_ms);
+  if (rc) return rc;
+  uint64_t new_cap = ctx->utxo_cap; /* capacity 0: a pure compaction */
+  if (capacity) {
+    if (capacity > (1ULL << 40)) {
+      set_error("kv_utxo_rehash: capacity out of range");
+      return -1;
+    }
+    new_cap = 64;
+    while (new_cap < capacity * 2) new_cap <<= 1; /* as kv_utxo_reset */
+    if (new_cap < 2 * scan.n_live) {
+      set_error("kv_utxo_rehash: capacity too small for the live set");
+      return -3;
+    }
+  }
+  if (scan.arena_live_bytes > 0xffffffffULL || scan.n_arena > 0xffffffffULL) {
+    set_error("kv_utxo_rehash: compacted arena exceeds a u32 offset");
+    return -3;
+  }
+  /* the fresh arena: arena_reserve's rounding (1 MiB doubled until it fits);
+   * a context that already owns an arena keeps at least that minimum */
+  uint64_t new_arena_cap = 0;
+  if (ctx->d_arena || scan.arena_live_bytes) {
+    new_arena_cap = 1u << 20;
+    while (new_arena_cap < scan.arena_live_bytes) new_arena_cap *= 2;
+  }
+  const uint32_t jobs_cap = (uint32_t)scan.n_arena;
+  rc = commit_scratch(ctx, 0); /* index list and count word */
+  if (rc) return rc;
+  if (jobs_cap && ensure_cap(&ctx->d_gjobs, &ctx->d_gjobs_cap,
+                             (size_t)jobs_cap * sizeof(kv::arena_gather_job)))
+    return -2;
+
+  kv::utxo_slot *nt = nullptr;
+  uint8_t *na = nullptr;
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  auto discard = [&]() { /* every failure below leaves the old table in place */
+    if (nt) (void)hipFree(nt);
+    if (na) (void)hipFree(na);
+    if (t0) (void)hipEventDestroy(t0);
+    if (t1) (void)hipEventDestroy(t1);
+  };
+  if (hipMalloc(&nt, new_cap * sizeof(kv::utxo_slot)) != hipSuccess) {
+    nt = nullptr;
+    (void)hipGetLastError();
+    set_error("kv_utxo_rehash: hipMalloc failed (table)");
+    return -2;
+  }
+  if (new_arena_cap && hipMalloc(&na, new_arena_cap) != hipSuccess) {
+    na = nullptr;
+    (void)hipGetLastError();
+    discard();
+    set_error("kv_utxo_rehash: hipMalloc failed (arena)");
+    return -2;
+  }
+  uint8_t *fx = ctx->d_cm_fixed;
+  uint32_t *d_count = (uint32_t *)(fx + CM_OFF_COUNT);
+  uint32_t *d_idx = (uint32_t *)(fx + CM_OFF_IDX);
+  kv::rehash_rec *d_rec = (kv::rehash_rec *)(ctx->d_tbl_rec + TR_OFF_REHASH);
+  kv::rehash_rec h_rec;
+  hipError_t e = hipEventCreate(&t0);
+  if (e == hipSuccess) e = hipEventCreate(&t1);
+  if (e == hipSuccess) e = hipEventRecord(t0, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(nt, 0, new_cap * sizeof(kv::utxo_slot), ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(d_rec, 0, sizeof(kv::rehash_rec), ctx->stream);
+  for (uint64_t base = 0; e == hipSuccess && base < ctx->utxo_cap;
+       base += KV_COMMIT_WINDOW) {
+    uint32_t n_slots = (uint32_t)std::min<uint64_t>(KV_COMMIT_WINDOW,
+                                                    ctx->utxo_cap - base);
+    dim3 grid((n_slots + 255) / 256);
+    e = hipMemsetAsync(d_count, 0, 16, ctx->stream);
+    if (e != hipSuccess) break;
+    hipLaunchKernelGGL(kv::kv_utxo_commit_compact_kernel, grid, dim3(256), 0,
+                       ctx->stream, ctx->d_utxo, base, n_slots, d_idx, d_count);
+    hipLaunchKernelGGL(kv::kv_utxo_rehash_insert_kernel, grid, dim3(256), 0,
+                       ctx->stream, (const kv::utxo_slot *)ctx->d_utxo, base,
+                       (const uint32_t *)d_idx, (const uint32_t *)d_count, nt,
+                       new_cap - 1, ctx->arena_head, new_arena_cap,
+                       (kv::arena_gather_job *)ctx->d_gjobs, jobs_cap, d_rec);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && jobs_cap) {
+    hipLaunchKernelGGL(kv::kv_arena_copy_jobs_kernel, dim3(jobs_cap), dim3(256), 0,
+                       ctx->stream, (const uint8_t *)ctx->d_arena,
+                       (const kv::arena_gather_job *)ctx->d_gjobs,
+                       (const uint32_t *)&d_rec->n_jobs, jobs_cap, na);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(&h_rec, d_rec, sizeof(kv::rehash_rec), hipMemcpyDeviceToHost,
+                       ctx->stream);
+  if (e == hipSuccess) e = hipEventRecord(t1, ctx->stream);
+  /* the single synchronisation of the chain */
+  hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  float ms = 0.f;
+  if (e == hipSuccess && e2 == hipSuccess) (void)hipEventElapsedTime(&ms, t0, t1);
+  if (e != hipSuccess || e2 != hipSuccess) {
+    discard();
+    HIP_CHECK(e);
+    HIP_CHECK(e2);
+  }
+  if (h_rec.fail || h_rec.inserted != scan.n_live ||
+      h_rec.arena_head != scan.arena_live_bytes) {
+    discard();
+    set_error(h_rec.fail
+                  ? "kv_utxo_rehash: an entry could not be placed (script reference "
+                    "out of range, or no room)"
+                  : "kv_utxo_rehash: inserted count differs from the live count");
+    return -3;
+  }
+  /* device work complete and clean: swap, then free the old allocations */
+  kv::utxo_slot *old_t = ctx->d_utxo;
+  uint8_t *old_a = ctx->d_arena;
+  ctx->d_utxo = nt;
+  ctx->utxo_cap = new_cap;
+  ctx->d_arena = na;
+  ctx->arena_cap = new_arena_cap;
+  ctx->arena_head = h_rec.arena_head;
+  nt = nullptr;
+  na = nullptr;
+  discard(); /* the events */
+  (void)hipFree(old_t);
+  if (old_a) (void)hipFree(old_a);
+  if (kernel_ms) *kernel_ms = (double)scan_ms + (double)ms;
+  return 0;
+}
+
+extern "C" int kv_utxo_export_chunk(kv_ctx *ctx, uint64_t *cursor, size_t max_entries,
+                                    uint8_t *outpoints_out, uint8_t *entries_out,
+                                    uint8_t *spk_out, size_t spk_cap, size_t *spk_used,
+                                    size_t *n_out) {
+  if (!ctx || !cursor || !n_out) {
+    set_error("kv_utxo_export_chunk: null argument");
+    return -1;
+  }
+  *n_out = 0;
+  if (spk_used) *spk_used = 0;
+  if (spk_cap < KV_UTXO_MAX_SPK || !spk_out) {
+    set_error("kv_utxo_export_chunk: spk_cap below KV_UTXO_MAX_SPK");
+    return -1;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  (void)hipGetLastError(); /* clear any stale per-thread error so the
+      launch-config checks below only see THIS call's launches */
+  if (*cursor >= ctx->utxo_cap) { /* the walk is over (or there is no table) */
+    *cursor = ctx->utxo_cap;
+    return 0;
+  }
+  if (max_entries == 0) return 0;
+  if (!outpoints_out || !entries_out) {
+    set_error("kv_utxo_export_chunk: null argument");
+    return -1;
+  }
+  /* the span: about max_entries live slots at the 50% design load, at least
+   * 4096 slots so a sparse table is not walked a handful of slots per call,
+   * at most one window, never past the end or across a window boundary */
+  const uint64_t base = *cursor;
+  uint64_t want = max_entries > KV_COMMIT_WINDOW ? KV_COMMIT_WINDOW : 2 * max_entries;
+  want = std::max<uint64_t>(want, 4096);
+  uint64_t to_boundary = KV_COMMIT_WINDOW - (base & (KV_COMMIT_WINDOW - 1));
+  const uint32_t span = (uint32_t)std::min<uint64_t>(
+      std::min<uint64_t>(want, to_boundary), ctx->utxo_cap - base);
+  int rc = commit_scratch(ctx, 0);
+  if (rc) return rc;
+  if (ensure_cap((void **)&ctx->d_op_in, &ctx->d_op_cap, (size_t)span * 36) ||
+      ensure_cap((void **)&ctx->d_ent_out, &ctx->d_ent_cap, (size_t)span * 64) ||
+      ensure_cap((void **)&ctx->d_exp_refs, &ctx->d_exp_refs_cap, (size_t)span * 8))
+    return -2;
+  uint8_t *fx = ctx->d_cm_fixed;
+  uint32_t *d_count = (uint32_t *)(fx + CM_OFF_COUNT);
+  uint32_t *d_idx = (uint32_t *)(fx + CM_OFF_IDX);
+  dim3 grid((span + 255) / 256);
+  HIP_CHECK(hipMemsetAsync(d_count, 0, 16, ctx->stream));
+  hipLaunchKernelGGL(kv::kv_utxo_commit_compact_kernel, grid, dim3(256), 0,
+                     ctx->stream, ctx->d_utxo, base, span, d_idx, d_count);
+  hipLaunchKernelGGL(kv::kv_utxo_export_gather_kernel, grid, dim3(256), 0,
+                     ctx->stream, (const kv::utxo_slot *)ctx->d_utxo, base,
+                     (const uint32_t *)d_idx, (const uint32_t *)d_count,
+                     ctx->arena_head, ctx->d_op_in, ctx->d_ent_out, ctx->d_exp_refs);
+  HIP_CHECK(hipGetLastError());
+  uint32_t count = 0;
+  HIP_CHECK(hipMemcpyAsync(&count, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (count > span) {
+    set_error("kv_utxo_export_chunk: compaction count out of range");
+    return -2;
+  }
+  if (count == 0) {
+    *cursor = base + span;
+    return 0;
+  }
+  std::vector<uint32_t> idx(count);
+  std::vector<unsigned long long> refs(count);
+  std::vector<uint8_t> &keys = ctx->ops_buf, &vals = ctx->ent_buf;
+  keys.resize((size_t)count * 36);
+  vals.resize((size_t)count * 64);
+  HIP_CHECK(hipMemcpyAsync(idx.data(), d_idx, (size_t)count * 4,
+                           hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(refs.data(), ctx->d_exp_refs, (size_t)count * 8,
+                           hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(keys.data(), ctx->d_op_in, (size_t)count * 36,
+                           hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(vals.data(), ctx->d_ent_out, (size_t)count * 64,
+                           hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  /* compaction order is whatever the waves' atomics made it: sort into slot
+   * order, then take the prefix that fits max_entries and spk_cap */
+  std::vector<uint32_t> order(count);
+  for (uint32_t i = 0; i < count; i++) order[i] = i;
+  std::sort(order.begin(), order.end(),
+            [&](uint32_t a, uint32_t b) { return idx[a] < idx[b]; });
+  std::vector<kv::arena_gather_job> jobs;
+  size_t m = 0;
+  uint32_t used = 0;
+  for (; m < count && m < max_entries; m++) {
+    uint32_t p = order[m];
+    if (refs[p] == KV_EXPORT_REF_BAD) {
+      set_error("kv_utxo_export_chunk: a table entry's script reference is out of range");
+      return -3;
+    }
+    uint32_t spk_len = (uint32_t)(refs[p] >> 32);
+    if (spk_len) {
+      if ((size_t)used + spk_len > spk_cap) break; /* next chunk starts here */
+      jobs.push_back(kv::arena_gather_job{(uint32_t)refs[p], spk_len, used, 0});
+      used += spk_len;
+    }
+    memcpy(outpoints_out + m * 36, keys.data() + (size_t)p * 36, 36);
+    memcpy(entries_out + m * 64, vals.data() + (size_t)p * 64, 64);
+  }
+  if (!jobs.empty()) {
+    if (ensure_cap(&ctx->d_gjobs, &ctx->d_gjobs_cap,
+                   jobs.size() * sizeof(kv::arena_gather_job)) ||
+        ensure_cap(&ctx->d_gout, &ctx->d_gout_cap, used))
+      return -2;
+    HIP_CHECK(hipMemcpyAsync(ctx->d_gjobs, jobs.data(),
+                             jobs.size() * sizeof(kv::arena_gather_job),
+                             hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(kv::kv_arena_gather_kernel, dim3((uint32_t)jobs.size()),
+                       dim3(256), 0, ctx->stream, ctx->d_arena,
+                       (const kv::arena_gather_job *)ctx->d_gjobs,
+                       (uint32_t)jobs.size(), (uint8_t *)ctx->d_gout);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(spk_out, ctx->d_gout, used, hipMemcpyDeviceToHost,
+                             ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  }
+  /* m >= 1 here: the first entry always fits (spk_cap >= KV_UTXO_MAX_SPK) */
+  *cursor = m == count ? base + span : base + (uint64_t)idx[order[m - 1]] + 1;
+  *n_out = m;
+  if (spk_used) *spk_used = used;
   return 0;
 }
 

@@ -83,26 +83,32 @@ extern "C" __global__ void kv_utxo_upsert_kernel(utxo_slot *table, uint64_t cap_
     uint64_t slot = home;
     int restart = 0;
     uint64_t probe = 0;
-    for (; probe <= cap_mask; probe++, slot = (slot + 1) & cap_mask) {
-      utxo_slot *s = &table[slot];
-      uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_ACQUIRE,
-                                      __HIP_MEMORY_SCOPE_AGENT);
-      /* wait for a concurrent claimer of this slot to publish its key */
-      while (st == KV_SLOT_CLAIMED)
-        st = __hip_atomic_load(&s->state, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-      if (st == KV_SLOT_READY) {
-        if (key_eq(s->key, key)) { /* overwrite value (upsert semantics) */
-          for (int k = 0; k < 64; k++) s->value[k] = val[k];
-          return;
+    for (; probe <= cap_mask + 1; probe++, slot = (slot + 1) & cap_mask) {
+      if (probe <= cap_mask) {
+        utxo_slot *s = &table[slot];
+        uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_ACQUIRE,
+                                        __HIP_MEMORY_SCOPE_AGENT);
+        /* wait for a concurrent claimer of this slot to publish its key */
+        while (st == KV_SLOT_CLAIMED)
+          st = __hip_atomic_load(&s->state, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        if (st == KV_SLOT_READY) {
+          if (key_eq(s->key, key)) { /* overwrite value (upsert semantics) */
+            for (int k = 0; k < 64; k++) s->value[k] = val[k];
+            return;
+          }
+          continue;
         }
-        continue;
+        if (st == KV_SLOT_TOMB) {
+          if (cand == ~0ULL) cand = slot;
+          continue; /* keep probing: the key may live further down the chain */
+        }
+      } else if (cand == ~0ULL) {
+        break; /* every slot holds another key: the table is full */
       }
-      if (st == KV_SLOT_TOMB) {
-        if (cand == ~0ULL) cand = slot;
-        continue; /* keep probing: the key may live further down the chain */
-      }
-      /* EMPTY: end of this key's chain — the key is absent. Claim the
-       * remembered tombstone if any, else this empty slot. */
+      /* EMPTY, or every slot probed with no EMPTY left (a table whose free
+       * slots are all tombstones is not full): end of this key's chain — the
+       * key is absent. Claim the remembered tombstone if any, else this empty
+       * slot. */
       {
         uint64_t tgt = (cand != ~0ULL) ? cand : slot;
         uint32_t expected = (cand != ~0ULL) ? KV_SLOT_TOMB : KV_SLOT_EMPTY;

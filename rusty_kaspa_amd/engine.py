@@ -26,6 +26,14 @@ class KvCacheStats(ctypes.Structure):
                 ("misses", ctypes.c_uint64)]
 
 
+class KvUtxoTableStats(ctypes.Structure):
+    _fields_ = [("slots", ctypes.c_uint64), ("n_live", ctypes.c_uint64),
+                ("n_tomb", ctypes.c_uint64), ("n_empty", ctypes.c_uint64),
+                ("arena_used", ctypes.c_uint64),
+                ("arena_live_bytes", ctypes.c_uint64),
+                ("arena_cap", ctypes.c_uint64)]
+
+
 def load_library() -> ctypes.CDLL:
     if not os.path.exists(_LIB_PATH):
         raise RuntimeError(
@@ -167,6 +175,46 @@ class Engine:
             ctypes.c_void_p(self.ctx), outpoints, entries64, spk_blob,
             ctypes.c_size_t(len(spk_blob)), ctypes.c_size_t(n), buf)
         self._check(rc)
+
+    def utxo_stats(self) -> dict:
+        """Occupancy of the GPU-resident UTXO table and its script arena
+        (kv_utxo_stats): slots, n_live, n_tomb, n_empty, arena_used,
+        arena_live_bytes, arena_cap. All zeros before the first reset."""
+        out = KvUtxoTableStats()
+        self._check(self.lib.kv_utxo_stats(ctypes.c_void_p(self.ctx),
+                                           ctypes.byref(out)))
+        return {name: getattr(out, name) for name, _ in out._fields_}
+
+    def utxo_rehash(self, capacity: int = 0) -> float:
+        """Rebuild the table and arena in place (kv_utxo_rehash): grow or
+        shrink to `capacity` entries, or compact tombstones and arena garbage
+        at the current size with capacity=0. Returns kernel_ms. Raises, with
+        the old table untouched, if the call fails."""
+        ms = ctypes.c_double()
+        rc = self.lib.kv_utxo_rehash(ctypes.c_void_p(self.ctx),
+                                     ctypes.c_uint64(capacity), ctypes.byref(ms))
+        self._check(rc)
+        return ms.value
+
+    def utxo_export_chunk(self, cursor: int, max_entries: int,
+                          spk_cap: int = 1 << 20):
+        """One step of the export walk (kv_utxo_export_chunk), from slot
+        `cursor`: (cursor, outpoints, entries, spk_blob, n), in the input
+        format of utxo_import_chunk. The walk is over when the returned cursor
+        equals utxo_stats()["slots"] and n == 0."""
+        cur = ctypes.c_uint64(cursor)
+        ops = (ctypes.c_uint8 * (36 * max(max_entries, 1)))()
+        ents = (ctypes.c_uint8 * (64 * max(max_entries, 1)))()
+        spk = (ctypes.c_uint8 * max(spk_cap, 1))()
+        used, n = ctypes.c_size_t(), ctypes.c_size_t()
+        rc = self.lib.kv_utxo_export_chunk(
+            ctypes.c_void_p(self.ctx), ctypes.byref(cur),
+            ctypes.c_size_t(max_entries), ops, ents, spk,
+            ctypes.c_size_t(spk_cap), ctypes.byref(used), ctypes.byref(n))
+        self._check(rc)
+        return (cur.value, ctypes.string_at(ops, 36 * n.value),
+                ctypes.string_at(ents, 64 * n.value),
+                ctypes.string_at(spk, used.value), n.value)
 
     def sig_cache_stats(self):
         out = KvCacheStats()
