@@ -1033,7 +1033,6 @@ static int stage_reserve(kv_ctx *ctx, size_t need) {
   ctx->h_stage_off = 0;
   if (ctx->h_stage_cap >= need) return 0;
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-  if (ctx->h_mu_partial) (void)hipHostFree(ctx->h_mu_partial);
   size_t nc = need + need / 2 + 4096;
   if (hipHostMalloc(&ctx->h_stage, nc) != hipSuccess) {
     ctx->h_stage = nullptr;
@@ -1901,10 +1900,6 @@ static int arena_reserve(kv_ctx *ctx, uint64_t need) {
     HIP_CHECK(hipMemcpyAsync(na, ctx->d_arena, ctx->arena_head,
                              hipMemcpyDeviceToDevice, ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (ctx->h_s_status) (void)hipHostFree(ctx->h_s_status);
-  if (ctx->h_e_status) (void)hipHostFree(ctx->h_e_status);
-  if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-  if (ctx->h_mu_partial) (void)hipHostFree(ctx->h_mu_partial);
   if (ctx->d_arena) (void)hipFree(ctx->d_arena);
   ctx->d_arena = na;
   ctx->arena_cap = nc;
@@ -2812,11 +2807,15 @@ extern "C" int kv_block_body_check(kv_ctx *ctx, const uint8_t *blob,
       for (int i = 0; i < n_txs; i++) pres[i] = 1;
       static const uint8_t ZERO[32] = {0};
       size_t width = pot;
+      /* each level is written into its own buffer: with 256 or more parents
+       * the level is fanned over the host threads, and parent o of one thread
+       * sits where another thread still reads children 2o', 2o'+1 */
+      std::vector<uint8_t> nxt(pot / 2 * 32, 0), npres(pot / 2, 0);
       while (width > 1) {
         kvh_parallel_for((uint32_t)(width / 2), [&](uint32_t o) {
           size_t i = 2 * (size_t)o;
           if (!pres[i]) {
-            pres[o] = 0;
+            npres[o] = 0;
             return;
           }
           uint8_t buf[64];
@@ -2825,9 +2824,11 @@ extern "C" int kv_block_body_check(kv_ctx *ctx, const uint8_t *blob,
           uint8_t h[32];
           static const uint8_t MKEY[] = "MerkleBranchHash";
           h_blake2b_keyed(MKEY, sizeof(MKEY) - 1, buf, 64, h);
-          memcpy(cur.data() + o * 32, h, 32);
-          pres[o] = 1;
+          memcpy(nxt.data() + o * 32, h, 32);
+          npres[o] = 1;
         });
+        cur.swap(nxt);
+        pres.swap(npres);
         width /= 2;
       }
       memcpy(merkle_root_out, cur.data(), 32);
@@ -3155,4 +3156,71 @@ extern "C" int kv_test_storage_mass(uint32_t n_ins, const uint64_t *in_amounts,
     tx.outputs.push_back(o);
   }
   return kvh_storage_mass(tx, /*is_coinbase=*/false, mass_out);
+}
+
+/* ---- direct reduce-kernel test export (tests/test_gpu_u3072_wave.py): one
+ * launch of the wave-cooperative U3072 reduce over caller-supplied operands,
+ * with the launch shape every production site uses ((stride+3)/4 blocks of
+ * 256). acc_in == NULL runs kv_u3072_reduce_wave_kernel; otherwise the
+ * `stride` accumulators are uploaded and kv_u3072_reduce_wave_acc_kernel runs
+ * with a host-known count. out receives the `stride` results. ---- */
+
+extern "C" int kv_test_u3072_reduce(kv_ctx *ctx, const uint64_t *elements, uint32_t n,
+                                    uint32_t stride, const uint64_t *acc_in,
+                                    uint64_t *out, uint64_t *n_live_out) {
+  if (!ctx || !out || stride == 0 || (n && !elements)) {
+    set_error("kv_test_u3072_reduce: bad argument");
+    return -1;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  (void)hipGetLastError(); /* clear any stale per-thread error so the
+      launch-config checks below only see THIS call's launches */
+  const size_t elem_bytes = KVU_LIMBS * sizeof(uint64_t);
+  DeviceBuf d_elems, d_res, d_rec;
+  int rc = 0;
+  kv::commit_out h_rec;
+  hipError_t e = hipSuccess;
+  if (d_elems.ensure((n ? n : 1) * elem_bytes) || d_res.ensure(stride * elem_bytes) ||
+      d_rec.ensure(sizeof(kv::commit_out))) {
+    rc = -2;
+    goto done;
+  }
+#define KV_TRY(expr)                                                           \
+  if ((e = (expr)) != hipSuccess) {                                            \
+    set_error_loc(hipGetErrorString(e), __FILE__, __LINE__, #expr);            \
+    rc = -2;                                                                   \
+    goto done;                                                                 \
+  }
+  if (n)
+    KV_TRY(hipMemcpyAsync(d_elems.p, elements, n * elem_bytes, hipMemcpyHostToDevice,
+                          ctx->stream));
+  if (acc_in) {
+    KV_TRY(hipMemcpyAsync(d_res.p, acc_in, stride * elem_bytes, hipMemcpyHostToDevice,
+                          ctx->stream));
+    KV_TRY(hipMemsetAsync(d_rec.p, 0, sizeof(kv::commit_out), ctx->stream));
+    hipLaunchKernelGGL(kv_u3072_reduce_wave_acc_kernel, dim3((stride + 3) / 4),
+                       dim3(256), 0, ctx->stream, (const uint64_t *)d_elems.p,
+                       (const uint32_t *)nullptr, n, stride, (uint64_t *)d_res.p,
+                       (kv::commit_out *)d_rec.p);
+  } else {
+    hipLaunchKernelGGL(kv_u3072_reduce_wave_kernel, dim3((stride + 3) / 4), dim3(256),
+                       0, ctx->stream, (const uint64_t *)d_elems.p, n, stride,
+                       (uint64_t *)d_res.p);
+  }
+  KV_TRY(hipGetLastError());
+  KV_TRY(hipStreamSynchronize(ctx->stream));
+  KV_TRY(hipMemcpy(out, d_res.p, stride * elem_bytes, hipMemcpyDeviceToHost));
+  if (n_live_out) {
+    *n_live_out = 0;
+    if (acc_in) {
+      KV_TRY(hipMemcpy(&h_rec, d_rec.p, sizeof(h_rec), hipMemcpyDeviceToHost));
+      *n_live_out = h_rec.n_live;
+    }
+  }
+#undef KV_TRY
+done:
+  if (d_elems.p) (void)hipFree(d_elems.p);
+  if (d_res.p) (void)hipFree(d_res.p);
+  if (d_rec.p) (void)hipFree(d_rec.p);
+  return rc;
 }

@@ -121,6 +121,24 @@ class Engine:
         rc = self.lib.kv_muhash_combine(ctypes.c_void_p(self.ctx), buf, other768)
         self._check(rc)
 
+    def u3072_reduce_hook(self, elements: bytes, n: int, stride: int,
+                          acc: bytes | None = None):
+        """Test hook (kv_test_u3072_reduce): one launch of the wave U3072
+        reduce over `n` 384-byte LE elements. Without `acc`, wave w returns
+        elements[w]·elements[w+stride]·… (one for an idle wave); with `acc`
+        (stride × 384 bytes) each wave multiplies its chain into its own
+        accumulator. Returns (stride × 384 result bytes, counted elements)."""
+        assert len(elements) == 384 * n
+        assert acc is None or len(acc) == 384 * stride
+        out = (ctypes.c_uint8 * (384 * stride))()
+        n_live = ctypes.c_uint64()
+        rc = self.lib.kv_test_u3072_reduce(
+            ctypes.c_void_p(self.ctx), elements if n else None,
+            ctypes.c_uint32(n), ctypes.c_uint32(stride), acc, out,
+            ctypes.byref(n_live))
+        self._check(rc)
+        return bytes(out), n_live.value
+
     def validate_block(self, blob: bytes, n_txs: int, pov_daa: int, block_daa: int,
                        flags: int = 2, want_muhash: bool = True, raw: bool = False):
         codes = (ctypes.c_int32 * n_txs)()
