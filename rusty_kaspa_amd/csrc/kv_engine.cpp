@@ -74,33 +74,99 @@ struct kv_sig_key_hash {
 #define KV_SCHNORR_SPLIT_MIN_DEFAULT ((size_t)1 << 18)
 #endif
 
+/* Owning, grow-on-demand buffers: every allocation of the engine is one of
+ * these two, so a pointer is freed exactly once and never outlives its
+ * capacity. OwnedBuf<false> is device memory, OwnedBuf<true> pinned host
+ * memory. Non-copyable; moves and swaps hand the allocation over. */
+template <bool PINNED> struct OwnedBuf {
+  void *p = nullptr;
+  size_t cap = 0;
+  OwnedBuf() = default;
+  OwnedBuf(const OwnedBuf &) = delete;
+  OwnedBuf &operator=(const OwnedBuf &) = delete;
+  OwnedBuf(OwnedBuf &&o) noexcept { swap(o); }
+  OwnedBuf &operator=(OwnedBuf &&o) noexcept {
+    swap(o);
+    return *this;
+  }
+  ~OwnedBuf() { reset(); }
+  void swap(OwnedBuf &o) noexcept {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+  }
+  void reset() {
+    if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+  }
+  /* a fresh allocation of exactly `bytes`; the old one is freed first */
+  int alloc(size_t bytes) {
+    reset();
+    if ((PINNED ? hipHostMalloc(&p, bytes) : hipMalloc(&p, bytes)) != hipSuccess) {
+      p = nullptr;
+      (void)hipGetLastError();
+      set_error(PINNED ? "hipHostMalloc failed" : "hipMalloc failed");
+      return -2;
+    }
+    cap = bytes;
+    return 0;
+  }
+  /* at least `need` bytes; growing drops the contents */
+  int ensure(size_t need) {
+    return cap >= need ? 0 : alloc(need + need / 2 + 256);
+  }
+  template <class T = uint8_t> T *as() const { return (T *)p; }
+};
+using DeviceBuf = OwnedBuf<false>;
+using PinnedBuf = OwnedBuf<true>;
+
+/* One verify lane: the device chain jobs -> tuples -> bitmap/status of one
+ * signature kind, plus the pinned landing buffer of its status readback. The
+ * two kinds differ only in the constants of LaneDesc and in which verify
+ * kernel runs. */
+struct LaneDesc {
+  uint32_t tuple_bytes; /* sig64 ‖ pk ‖ msg32 */
+  uint32_t msg_off;
+  int ecdsa;
+  int tev_assemble, tev_verify; /* start event of the timing pair in kv_ctx::tev */
+};
+enum { LANE_SCHNORR = 0, LANE_ECDSA = 1 }; /* = kv_job::ecdsa */
+
+struct VerifyLane {
+  const LaneDesc d;
+  DeviceBuf jobs, tuples, bitmap, status;
+  /* PINNED: a pageable-dest hipMemcpyAsync blocks the enqueue thread until the
+   * producing kernels finish, which serialized the three streams (measured
+   * 7.7ms of 8.3ms in the enqueue phase) */
+  PinnedBuf h_status;
+};
+
+/* per-context validate scratch. Per-ctx so two engine contexts in one process
+ * never share device scratch. */
+struct ValidateBufs {
+  DeviceBuf blob, subhashes, elem_jobs, elements, partials_a, partials_b, tx_hashes;
+  VerifyLane lane[2] = {{{128, 96, 0, 2, 6}}, {{132, 97, 1, 4, 8}}};
+};
+
 struct kv_ctx {
   kv_params params;
-  hipStream_t stream;
-  hipStream_t stream2; /* ecdsa verify chain (overlaps the schnorr chain) */
-  hipStream_t stream3; /* optimistic muhash chain (overlaps both) */
-  hipEvent_t ev_blob;  /* blob upload complete (sync-only, no timing) */
-  hipEvent_t ev_sub;   /* subhash kernel complete */
+  hipStream_t stream = nullptr;
+  hipStream_t stream2 = nullptr; /* ecdsa verify chain (overlaps the schnorr chain) */
+  hipStream_t stream3 = nullptr; /* optimistic muhash chain (overlaps both) */
+  hipEvent_t ev_blob = nullptr;  /* blob upload complete (sync-only, no timing) */
+  hipEvent_t ev_sub = nullptr;   /* subhash kernel complete */
   std::mutex mu;
   /* KIP-21 seq-commitment accessor (kv_set_seq_commit_accessor) */
   kv_seq_commit_accessor_fn seqc_fn = nullptr;
   void *seqc_user = nullptr;
-  /* per-context validate scratch (ValidateBufs; opaque here because the type
-   * lives with the validate section). Per-ctx so two engine contexts in one
-   * process never share device scratch. */
-  void *vb = nullptr;
+  ValidateBufs vb;
   /* per-kernel timing events of the last validate call (kv_get_validate_timings):
    * pairs (start,stop) for subhash, s-assemble, e-assemble, schnorr, ecdsa, muhash */
   hipEvent_t tev[12] = {};
   bool tev_init = false;
   kv_validate_timings last_timings = {};
   /* grow-on-demand device scratch */
-  uint8_t *d_in = nullptr;
-  size_t d_in_cap = 0;
-  uint64_t *d_bitmap = nullptr;
-  size_t d_bitmap_cap = 0;
-  uint8_t *d_status = nullptr;
-  size_t d_status_cap = 0;
+  DeviceBuf d_in, d_bitmap, d_status;
   uint64_t cache_hits = 0, cache_misses = 0, cache_insertions = 0;
   /* sig cache ⇔ TransactionValidator sig_cache (crypto/txscript/src/caches.rs:
    * 57-82): verdicts of (txid, entries-digest, input, hash-type, sig, pk)
@@ -110,73 +176,67 @@ struct kv_ctx {
   /* reusable populate-path scratch (capacity persists across calls — a fresh
    * multi-MB vector per block showed up as page-fault spikes in the bench) */
   std::vector<uint8_t> pop_buf, ops_buf, ent_buf;
-  /* PINNED host buffers for the verify-status readbacks: a pageable-dest
-   * hipMemcpyAsync blocks the enqueue thread until the producing kernels
-   * finish, which serialized the three streams (measured 7.7ms of 8.3ms in
-   * the enqueue phase) */
-  uint8_t *h_s_status = nullptr, *h_e_status = nullptr;
-  size_t h_s_cap = 0, h_e_cap = 0;
   /* per-call PINNED upload staging arena: hipMemcpyAsync from pageable host
    * memory blocks the enqueue thread (synchronous staging inside HIP); all
    * per-call H2D uploads bounce through this bump arena instead. Regions
    * stay valid until the call's final stream syncs. */
-  uint8_t *h_stage = nullptr;
-  size_t h_stage_cap = 0, h_stage_off = 0;
-  uint8_t *h_mu_partial = nullptr; /* pinned 768B muhash partial landing pad:
+  PinnedBuf h_stage;
+  size_t h_stage_off = 0;
+  PinnedBuf h_mu_partial; /* pinned 768B muhash partial landing pad:
     a pageable-dest D2H of even 384B blocks the enqueue thread until the
     whole reduce chain drains (measured ~3.9ms) */
   std::vector<uint64_t> found_buf;
   /* GPU-resident UTXO set */
-  kv::utxo_slot *d_utxo = nullptr;
+  DeviceBuf d_utxo;      /* kv::utxo_slot[utxo_cap] */
   uint64_t utxo_cap = 0; /* power of two */
-  /* out-of-line spk arena (entries with spk_len > 36; flags bit1) */
-  uint8_t *d_arena = nullptr;
-  uint64_t arena_cap = 0, arena_head = 0;
-  void *d_gjobs = nullptr;
-  size_t d_gjobs_cap = 0;
-  void *d_gout = nullptr;
-  size_t d_gout_cap = 0;
-  int *d_utxo_fail = nullptr;
-  uint8_t *d_op_in = nullptr;
-  size_t d_op_cap = 0;
-  uint8_t *d_val_in = nullptr;
-  size_t d_val_cap = 0;
-  uint8_t *d_ent_out = nullptr;
-  size_t d_ent_cap = 0;
+  kv::utxo_slot *table() const { return d_utxo.as<kv::utxo_slot>(); }
+  /* out-of-line spk arena (entries with spk_len > 36; flags bit1); its
+   * capacity is d_arena.cap */
+  DeviceBuf d_arena;
+  uint64_t arena_head = 0;
+  DeviceBuf d_gjobs, d_gout;
+  DeviceBuf d_utxo_fail; /* int; per-ctx: a shared flag would race when two
+                            contexts upsert concurrently */
+  DeviceBuf d_op_in, d_val_in, d_ent_out;
   /* UTXO commitment scratch (kv_utxo_commit_kernels.hip): sized by the
    * compiled window, never by table capacity. d_cm_fixed holds, in order, the
    * copy-back record, the window's live count, the slot index list, the
    * running accumulators and the final reduce's two partial buffers. */
-  uint8_t *d_cm_fixed = nullptr;
-  uint64_t *d_cm_elems = nullptr;
-  size_t d_cm_elems_cap = 0;
+  DeviceBuf d_cm_fixed, d_cm_elems;
   /* table maintenance (kv_utxo_rehash_kernels.hip): the two small copy-back
    * records of kv_utxo_stats / kv_utxo_rehash, and the export walk's per-entry
    * script references */
-  uint8_t *d_tbl_rec = nullptr;
-  unsigned long long *d_exp_refs = nullptr;
-  size_t d_exp_refs_cap = 0;
+  DeviceBuf d_tbl_rec, d_exp_refs;
   /* split Schnorr verify (launch_schnorr_verify): the ladder kernel's R limbs
-   * and pre-status, 121 B per signature. Written and read on ctx->stream only,
-   * under ctx->mu. */
-  uint8_t *d_sfin = nullptr;
-  size_t d_sfin_cap = 0;
+   * and pre-status, 121 B per signature. One split verify is in flight per
+   * context at a time (ctx->mu held, every caller syncs before the next). */
+  DeviceBuf d_sfin;
   size_t schnorr_split_min = KV_SCHNORR_SPLIT_MIN_DEFAULT;
+
+  /* handles are null until kv_create made them: it deletes a half-built
+   * context on failure. The buffers free themselves after this body. */
+  ~kv_ctx() {
+    if (stream) (void)hipStreamDestroy(stream);
+    if (stream2) (void)hipStreamDestroy(stream2);
+    if (stream3) (void)hipStreamDestroy(stream3);
+    if (ev_blob) (void)hipEventDestroy(ev_blob);
+    if (ev_sub) (void)hipEventDestroy(ev_sub);
+    if (tev_init)
+      for (int i = 0; i < 12; i++) (void)hipEventDestroy(tev[i]);
+  }
 };
 
-static int ensure_cap(void **ptr, size_t *cap, size_t need) {
-  if (*cap >= need) return 0;
-  if (*ptr) (void)hipFree(*ptr);
-  size_t newcap = need + need / 2;
-  if (hipMalloc(ptr, newcap) != hipSuccess) {
-    *ptr = nullptr;
-    *cap = 0;
-    set_error("hipMalloc failed");
-    return -2;
-  }
-  *cap = newcap;
-  return 0;
-}
+/* First line of every extern "C" entry that takes the lock: a null ctx is an
+ * error (-1), the context is locked for the rest of the call, and any stale
+ * per-thread HIP error is cleared so the launch-config checks below only see
+ * THIS call's launches. */
+#define KV_ENTER(ctx)                                                          \
+  if (!(ctx)) {                                                                \
+    set_error((std::string(__func__) + ": null ctx").c_str());                 \
+    return -1;                                                                 \
+  }                                                                            \
+  std::lock_guard<std::mutex> lk((ctx)->mu);                                   \
+  (void)hipGetLastError()
 
 extern "C" kv_ctx *kv_create(const kv_params *params) {
   int count = 0;
@@ -221,71 +281,40 @@ extern "C" kv_ctx *kv_create(const kv_params *params) {
   return ctx;
 }
 
-namespace {
-void kv_vb_release(void *vb); /* defined with ValidateBufs below */
-}
-
 extern "C" void kv_destroy(kv_ctx *ctx) {
   if (!ctx) return;
-  if (ctx->vb) kv_vb_release(ctx->vb);
-  if (ctx->d_in) (void)hipFree(ctx->d_in);
-  if (ctx->d_bitmap) (void)hipFree(ctx->d_bitmap);
-  if (ctx->d_status) (void)hipFree(ctx->d_status);
-  if (ctx->h_s_status) (void)hipHostFree(ctx->h_s_status);
-  if (ctx->h_e_status) (void)hipHostFree(ctx->h_e_status);
-  if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-  if (ctx->h_mu_partial) (void)hipHostFree(ctx->h_mu_partial);
-  if (ctx->d_arena) (void)hipFree(ctx->d_arena);
-  if (ctx->d_gjobs) (void)hipFree(ctx->d_gjobs);
-  if (ctx->d_gout) (void)hipFree(ctx->d_gout);
-  (void)hipStreamDestroy(ctx->stream);
-  (void)hipStreamDestroy(ctx->stream2);
-  (void)hipStreamDestroy(ctx->stream3);
-  (void)hipEventDestroy(ctx->ev_blob);
-  (void)hipEventDestroy(ctx->ev_sub);
-  if (ctx->tev_init)
-    for (int i = 0; i < 12; i++) (void)hipEventDestroy(ctx->tev[i]);
-  if (ctx->d_utxo) (void)hipFree(ctx->d_utxo);
-  if (ctx->d_utxo_fail) (void)hipFree(ctx->d_utxo_fail);
-  if (ctx->d_op_in) (void)hipFree(ctx->d_op_in);
-  if (ctx->d_val_in) (void)hipFree(ctx->d_val_in);
-  if (ctx->d_ent_out) (void)hipFree(ctx->d_ent_out);
-  if (ctx->d_sfin) (void)hipFree(ctx->d_sfin);
-  if (ctx->d_cm_fixed) (void)hipFree(ctx->d_cm_fixed);
-  if (ctx->d_cm_elems) (void)hipFree(ctx->d_cm_elems);
-  if (ctx->d_tbl_rec) (void)hipFree(ctx->d_tbl_rec);
-  if (ctx->d_exp_refs) (void)hipFree(ctx->d_exp_refs);
+  delete ctx; /* handles, then every buffer */
   (void)hipGetLastError(); /* teardown calls are fire-and-forget; do not leave
       their errors sticky for the next engine's launch checks (a swallowed
       invalid-argument here surfaced as a spurious failure in the NEXT
       context's first kernel-launch check) */
-  delete ctx;
 }
 
 /* ---------------- batched verify entry points ---------------- */
 
-/* Every Schnorr verify launch goes through here (ctx->mu held, ctx->stream):
- * the fused kernel below the split threshold, else ladder + batched finish
- * back to back on the same stream. Same outputs either way. */
-static int launch_schnorr_verify(kv_ctx *ctx, const uint8_t *d_tuples, size_t n,
+/* Every Schnorr verify launch goes through here (ctx->mu held): the fused
+ * kernel below the split threshold, else ladder + batched finish back to back
+ * on the same stream. Same outputs either way. */
+static int launch_schnorr_verify(kv_ctx *ctx, hipStream_t stream,
+                                 const uint8_t *d_tuples, size_t n,
                                  unsigned long long *d_bitmap, uint8_t *d_status) {
   if (n == 0) return 0;
   const unsigned long long grid = (n + 255) / 256;
   if (n < ctx->schnorr_split_min) {
     hipLaunchKernelGGL(kv::kv_schnorr_verify_kernel, dim3(grid), dim3(256), 0,
-                       ctx->stream, d_tuples, (unsigned long long)n, d_bitmap,
+                       stream, d_tuples, (unsigned long long)n, d_bitmap,
                        d_status);
     return 0;
   }
-  if (ensure_cap((void **)&ctx->d_sfin, &ctx->d_sfin_cap, n * 121)) return -2;
-  kv::u32 *limbs = (kv::u32 *)ctx->d_sfin;
-  uint8_t *pre = ctx->d_sfin + n * 120;
+  if (ctx->d_sfin.ensure(n * 121)) return -2;
+  kv::u32 *limbs = ctx->d_sfin.as<kv::u32>();
+  uint8_t *pre = ctx->d_sfin.as<uint8_t>() + n * 120;
   hipLaunchKernelGGL(kv::kv_schnorr_ladder_kernel, dim3(grid), dim3(256), 0,
-                     ctx->stream, d_tuples, (unsigned long long)n, limbs, pre);
+                     stream, d_tuples, (unsigned long long)n, limbs, pre);
   const unsigned long long lanes =
       ((n + KV_FINISH_K - 1) / KV_FINISH_K + 63) / 64 * 64;
   hipLaunchKernelGGL(kv::kv_schnorr_finish_kernel, dim3(lanes / 64), dim3(64), 0,
-                     ctx->stream, d_tuples, (unsigned long long)n,
+                     stream, d_tuples, (unsigned long long)n,
                      (const kv::u32 *)limbs, (const uint8_t *)pre, lanes, d_bitmap,
                      d_status);
   return 0;
@@ -304,7 +333,7 @@ extern "C" int kv_g_comb_fetch(kv_ctx *ctx, uint32_t first, uint32_t count,
     return -1;
   }
   if (count == 0) return 0;
-  std::lock_guard<std::mutex> lk(ctx->mu);
+  KV_ENTER(ctx);
   HIP_CHECK(hipMemcpyFromSymbolAsync(out64, HIP_SYMBOL(kv::KV_G_JOINT),
                                      (size_t)count * 64, (size_t)first * 64,
                                      hipMemcpyDeviceToHost, ctx->stream));
@@ -315,31 +344,29 @@ extern "C" int kv_g_comb_fetch(kv_ctx *ctx, uint32_t first, uint32_t count,
 static int verify_batch(kv_ctx *ctx, const uint8_t *tuples, size_t n, size_t rec_size,
                         int ecdsa, uint64_t *bitmap_out, uint8_t *status_out) {
   if (n == 0) return 0;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   size_t words = (n + 63) / 64;
-  if (ensure_cap((void **)&ctx->d_in, &ctx->d_in_cap, n * rec_size)) return -2;
-  if (ensure_cap((void **)&ctx->d_bitmap, &ctx->d_bitmap_cap, words * 8)) return -2;
-  if (ensure_cap((void **)&ctx->d_status, &ctx->d_status_cap, n)) return -2;
-  HIP_CHECK(hipMemcpyAsync(ctx->d_in, tuples, n * rec_size, hipMemcpyHostToDevice,
+  if (ctx->d_in.ensure(n * rec_size) || ctx->d_bitmap.ensure(words * 8) ||
+      ctx->d_status.ensure(n))
+    return -2;
+  uint8_t *d_in = ctx->d_in.as<uint8_t>();
+  unsigned long long *d_bitmap = ctx->d_bitmap.as<unsigned long long>();
+  uint8_t *d_status = status_out ? ctx->d_status.as<uint8_t>() : nullptr;
+  HIP_CHECK(hipMemcpyAsync(d_in, tuples, n * rec_size, hipMemcpyHostToDevice,
                            ctx->stream));
-  HIP_CHECK(hipMemsetAsync(ctx->d_bitmap, 0, words * 8, ctx->stream));
+  HIP_CHECK(hipMemsetAsync(d_bitmap, 0, words * 8, ctx->stream));
   int block = 256;
   unsigned long long grid = (n + block - 1) / block;
   if (ecdsa)
     hipLaunchKernelGGL(kv::kv_ecdsa_verify_kernel, dim3(grid), dim3(block), 0, ctx->stream,
-                       ctx->d_in, (unsigned long long)n, (unsigned long long *)ctx->d_bitmap,
-                       status_out ? ctx->d_status : nullptr);
-  else if (launch_schnorr_verify(ctx, ctx->d_in, n,
-                                 (unsigned long long *)ctx->d_bitmap,
-                                 status_out ? ctx->d_status : nullptr))
+                       d_in, (unsigned long long)n, d_bitmap, d_status);
+  else if (launch_schnorr_verify(ctx, ctx->stream, d_in, n, d_bitmap, d_status))
     return -2;
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpyAsync(bitmap_out, ctx->d_bitmap, words * 8, hipMemcpyDeviceToHost,
+  HIP_CHECK(hipMemcpyAsync(bitmap_out, d_bitmap, words * 8, hipMemcpyDeviceToHost,
                            ctx->stream));
   if (status_out)
-    HIP_CHECK(hipMemcpyAsync(status_out, ctx->d_status, n, hipMemcpyDeviceToHost,
+    HIP_CHECK(hipMemcpyAsync(status_out, d_status, n, hipMemcpyDeviceToHost,
                              ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return 0;
@@ -504,9 +531,7 @@ extern "C" int kv_muhash_finalize(kv_ctx *ctx, const uint8_t *partial768,
 
 extern "C" int kv_set_seq_commit_accessor(kv_ctx *ctx, kv_seq_commit_accessor_fn fn,
                                           void *user) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   ctx->seqc_fn = fn;
   ctx->seqc_user = user;
   return 0;
@@ -514,9 +539,7 @@ extern "C" int kv_set_seq_commit_accessor(kv_ctx *ctx, kv_seq_commit_accessor_fn
 
 extern "C" int kv_get_validate_timings(kv_ctx *ctx, kv_validate_timings *out) {
   if (!ctx || !out) return -1;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   *out = ctx->last_timings;
   return 0;
 }
@@ -537,23 +560,18 @@ extern "C" int kv_sig_cache_stats(kv_ctx *ctx, kv_cache_stats *out) {
 
 extern "C" int kv_stage_tuples(kv_ctx *ctx, const uint8_t *tuples, size_t n,
                                int ecdsa) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   size_t rec = ecdsa ? 132 : 128;
   size_t words = (n + 63) / 64;
-  if (ensure_cap((void **)&ctx->d_in, &ctx->d_in_cap, n * rec)) return -2;
-  if (ensure_cap((void **)&ctx->d_bitmap, &ctx->d_bitmap_cap, words * 8)) return -2;
-  HIP_CHECK(hipMemcpy(ctx->d_in, tuples, n * rec, hipMemcpyHostToDevice));
+  if (ctx->d_in.ensure(n * rec) || ctx->d_bitmap.ensure(words * 8)) return -2;
+  HIP_CHECK(hipMemcpy(ctx->d_in.p, tuples, n * rec, hipMemcpyHostToDevice));
   return 0;
 }
 
 /* run one staged verify launch; writes kernel milliseconds to *kernel_ms.
  * Does NOT copy the bitmap back (kv_fetch_bitmap does). */
 extern "C" int kv_verify_staged(kv_ctx *ctx, size_t n, int ecdsa, double *kernel_ms) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   int block = 256;
   unsigned long long grid = (n + block - 1) / block;
   hipEvent_t t0, t1;
@@ -562,10 +580,10 @@ extern "C" int kv_verify_staged(kv_ctx *ctx, size_t n, int ecdsa, double *kernel
   HIP_CHECK(hipEventRecord(t0, ctx->stream));
   if (ecdsa)
     hipLaunchKernelGGL(kv::kv_ecdsa_verify_kernel, dim3(grid), dim3(block), 0,
-                       ctx->stream, ctx->d_in, (unsigned long long)n,
-                       (unsigned long long *)ctx->d_bitmap, nullptr);
-  else if (launch_schnorr_verify(ctx, ctx->d_in, n,
-                                 (unsigned long long *)ctx->d_bitmap, nullptr))
+                       ctx->stream, ctx->d_in.as<uint8_t>(), (unsigned long long)n,
+                       ctx->d_bitmap.as<unsigned long long>(), nullptr);
+  else if (launch_schnorr_verify(ctx, ctx->stream, ctx->d_in.as<uint8_t>(), n,
+                                 ctx->d_bitmap.as<unsigned long long>(), nullptr))
     return -2; /* both kernels of the split path sit between t0 and t1 */
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipEventRecord(t1, ctx->stream));
@@ -579,11 +597,9 @@ extern "C" int kv_verify_staged(kv_ctx *ctx, size_t n, int ecdsa, double *kernel
 }
 
 extern "C" int kv_fetch_bitmap(kv_ctx *ctx, size_t n, uint64_t *bitmap_out) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   size_t words = (n + 63) / 64;
-  HIP_CHECK(hipMemcpy(bitmap_out, ctx->d_bitmap, words * 8, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(bitmap_out, ctx->d_bitmap.p, words * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -596,51 +612,6 @@ extern "C" int kv_fetch_bitmap(kv_ctx *ctx, size_t n, uint64_t *bitmap_out) {
 using namespace kvhost;
 
 namespace {
-
-struct DeviceBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t need) {
-    if (cap >= need) return 0;
-    if (p) (void)hipFree(p);
-    size_t nc = need + need / 2 + 256;
-    if (hipMalloc(&p, nc) != hipSuccess) {
-      p = nullptr;
-      cap = 0;
-      set_error("hipMalloc failed (validate)");
-      return -2;
-    }
-    cap = nc;
-    return 0;
-  }
-};
-
-struct ValidateBufs {
-  DeviceBuf blob, subhashes, s_jobs, e_jobs, s_tuples, e_tuples, s_bitmap, e_bitmap,
-      s_status, e_status, elem_jobs, elements, partials_a, partials_b, tx_hashes;
-  void release() {
-    DeviceBuf *bufs[] = {&blob, &subhashes, &s_jobs, &e_jobs, &s_tuples,
-                         &e_tuples, &s_bitmap, &e_bitmap, &s_status, &e_status,
-                         &elem_jobs, &elements, &partials_a, &partials_b,
-                         &tx_hashes};
-    for (auto *b : bufs) {
-      if (b->p) (void)hipFree(b->p);
-      b->p = nullptr;
-      b->cap = 0;
-    }
-  }
-};
-
-static ValidateBufs &vb_of(kv_ctx *ctx) {
-  if (!ctx->vb) ctx->vb = new ValidateBufs();
-  return *(ValidateBufs *)ctx->vb;
-}
-
-void kv_vb_release(void *p) {
-  auto *vb = (ValidateBufs *)p;
-  vb->release();
-  delete vb;
-}
 
 /* classify one input; appends jobs. Returns plan. */
 /* non-template scripts: run the host general interpreter (kv_script_host.inc)
@@ -925,91 +896,6 @@ static int resolve_input(const InputPlan &pl, const HInput &in, uint64_t sigop_u
 
 } // namespace
 
-extern "C" int kv_sighash_batch(kv_ctx *ctx, const uint8_t *blob, size_t blob_len,
-                                const kv_sighash_job *jobs_in, size_t n,
-                                uint8_t *hashes_out) {
-  /* standalone sighash service over the blob (tests/parity). Jobs are split by
-   * kind — the assemble kernel uses different tuple strides for schnorr (128B)
-   * and ecdsa (132B). */
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  ValidateBufs &vb = vb_of(ctx);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
-  vector<HTx> txs;
-  if (parse_blob_host(blob, blob_len, txs) < 0) {
-    set_error("kv_sighash_batch: malformed blob");
-    return -1;
-  }
-  std::vector<kv::kv_job> sjobs, ejobs;
-  std::vector<std::pair<int, size_t>> slots(n); /* (kind, index in its array) */
-  for (size_t i = 0; i < n; i++) {
-    const kv_sighash_job &j = jobs_in[i];
-    if (j.tx_index >= txs.size() || j.input_index >= txs[j.tx_index].inputs.size()) {
-      set_error("kv_sighash_batch: bad job index");
-      return -1;
-    }
-    const HInput &in = txs[j.tx_index].inputs[j.input_index];
-    kv::kv_job job{j.tx_index, in.rec_off, j.input_index, 0, 0, j.hash_type, j.ecdsa, 0};
-    if (j.ecdsa) {
-      slots[i] = {1, ejobs.size()};
-      ejobs.push_back(job);
-    } else {
-      slots[i] = {0, sjobs.size()};
-      sjobs.push_back(job);
-    }
-  }
-  uint32_t n_txs = (uint32_t)txs.size();
-  if (vb.blob.ensure(blob_len) || vb.subhashes.ensure((size_t)n_txs * 160))
-    return -2;
-  HIP_CHECK(hipMemcpyAsync(vb.blob.p, blob, blob_len, hipMemcpyHostToDevice,
-                           ctx->stream));
-  hipLaunchKernelGGL(kv::kv_tx_subhash_kernel, dim3((n_txs + 255) / 256), dim3(256), 0,
-                     ctx->stream, (const uint8_t *)vb.blob.p, n_txs,
-                     (uint8_t *)vb.subhashes.p);
-  std::vector<uint8_t> stuples(sjobs.size() * 128), etuples(ejobs.size() * 132);
-  if (!sjobs.empty()) {
-    if (vb.s_jobs.ensure(sjobs.size() * sizeof(kv::kv_job)) ||
-        vb.s_tuples.ensure(sjobs.size() * 128))
-      return -2;
-    HIP_CHECK(hipMemcpyAsync(vb.s_jobs.p, sjobs.data(),
-                             sjobs.size() * sizeof(kv::kv_job), hipMemcpyHostToDevice,
-                             ctx->stream));
-    hipLaunchKernelGGL(kv::kv_sighash_assemble_kernel,
-                       dim3(((uint32_t)sjobs.size() + 255) / 256), dim3(256), 0,
-                       ctx->stream, (const uint8_t *)vb.blob.p,
-                       (const uint8_t *)vb.subhashes.p,
-                       (const kv::kv_job *)vb.s_jobs.p, (uint32_t)sjobs.size(),
-                       (uint8_t *)vb.s_tuples.p, (uint8_t *)vb.s_tuples.p);
-    HIP_CHECK(hipMemcpyAsync(stuples.data(), vb.s_tuples.p, stuples.size(),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (!ejobs.empty()) {
-    if (vb.e_jobs.ensure(ejobs.size() * sizeof(kv::kv_job)) ||
-        vb.e_tuples.ensure(ejobs.size() * 132))
-      return -2;
-    HIP_CHECK(hipMemcpyAsync(vb.e_jobs.p, ejobs.data(),
-                             ejobs.size() * sizeof(kv::kv_job), hipMemcpyHostToDevice,
-                             ctx->stream));
-    hipLaunchKernelGGL(kv::kv_sighash_assemble_kernel,
-                       dim3(((uint32_t)ejobs.size() + 255) / 256), dim3(256), 0,
-                       ctx->stream, (const uint8_t *)vb.blob.p,
-                       (const uint8_t *)vb.subhashes.p,
-                       (const kv::kv_job *)vb.e_jobs.p, (uint32_t)ejobs.size(),
-                       (uint8_t *)vb.e_tuples.p, (uint8_t *)vb.e_tuples.p);
-    HIP_CHECK(hipMemcpyAsync(etuples.data(), vb.e_tuples.p, etuples.size(),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  }
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  for (size_t i = 0; i < n; i++) {
-    const uint8_t *msg = slots[i].first
-                             ? etuples.data() + slots[i].second * 132 + 97
-                             : stuples.data() + slots[i].second * 128 + 96;
-    memcpy(hashes_out + 32 * i, msg, 32);
-  }
-  return 0;
-}
-
 /* timing-event helpers (kv_get_validate_timings) */
 static void tev_ensure(kv_ctx *ctx) {
   if (ctx->tev_init) return;
@@ -1031,24 +917,14 @@ static double tev_ms(kv_ctx *ctx, int pair) {
  * idle — start of a validate call); returns -2 on allocation failure */
 static int stage_reserve(kv_ctx *ctx, size_t need) {
   ctx->h_stage_off = 0;
-  if (ctx->h_stage_cap >= need) return 0;
-  if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-  size_t nc = need + need / 2 + 4096;
-  if (hipHostMalloc(&ctx->h_stage, nc) != hipSuccess) {
-    ctx->h_stage = nullptr;
-    ctx->h_stage_cap = 0;
-    set_error("hipHostMalloc failed (staging)");
-    return -2;
-  }
-  ctx->h_stage_cap = nc;
-  return 0;
+  return ctx->h_stage.ensure(need);
 }
 
 /* copy src into the pinned arena and return the pinned pointer (NULL when the
  * arena is exhausted — callers then fall back to the pageable source) */
 static const uint8_t *stage_push(kv_ctx *ctx, const void *src, size_t len) {
-  if (!ctx->h_stage || ctx->h_stage_off + len > ctx->h_stage_cap) return nullptr;
-  uint8_t *dst = ctx->h_stage + ctx->h_stage_off;
+  if (!ctx->h_stage.p || ctx->h_stage_off + len > ctx->h_stage.cap) return nullptr;
+  uint8_t *dst = ctx->h_stage.as<uint8_t>() + ctx->h_stage_off;
   memcpy(dst, src, len);
   ctx->h_stage_off += len;
   return dst;
@@ -1063,6 +939,142 @@ static inline int h2d_staged(kv_ctx *ctx, void *dst, const void *src, size_t len
   return 0;
 }
 
+/* ---- the verify lane (VerifyLane): each step written once for both signature
+ * kinds, enqueued on the stream the caller names; nothing here synchronises.
+ * The blob and the subhashes must be resident in ctx->vb. `timed` is the
+ * call's timing-pair flags, or NULL to leave the lane's timing events alone
+ * (they describe phase 2 only). ---- */
+
+/* upload `jobs` and assemble one tuple (sig ‖ pk ‖ sighash) per job */
+static int lane_assemble(kv_ctx *ctx, VerifyLane &ln,
+                         const std::vector<kv::kv_job> &jobs, hipStream_t stream,
+                         bool *timed) {
+  const size_t n = jobs.size();
+  if (ln.jobs.ensure(n * sizeof(kv::kv_job)) ||
+      ln.tuples.ensure(n * ln.d.tuple_bytes))
+    return -2;
+  if (h2d_staged(ctx, ln.jobs.p, jobs.data(), n * sizeof(kv::kv_job), stream))
+    return -2;
+  if (timed) tev_rec(ctx, ln.d.tev_assemble, stream);
+  hipLaunchKernelGGL(kv::kv_sighash_assemble_kernel, dim3(((uint32_t)n + 255) / 256),
+                     dim3(256), 0, stream, ctx->vb.blob.as<const uint8_t>(),
+                     ctx->vb.subhashes.as<const uint8_t>(),
+                     ln.jobs.as<const kv::kv_job>(), (uint32_t)n,
+                     ln.tuples.as<uint8_t>(), ln.tuples.as<uint8_t>());
+  if (timed) {
+    tev_rec(ctx, ln.d.tev_assemble + 1, stream);
+    timed[ln.d.tev_assemble / 2] = true;
+  }
+  return 0;
+}
+
+/* upload host-built tuples; `mjobs` name the tuples whose message is a sighash
+ * the msg kernel still has to write in place (kv_job::sig_off = tuple slot) */
+static int lane_upload(kv_ctx *ctx, VerifyLane &ln, const std::vector<uint8_t> &tuples,
+                       const std::vector<kv::kv_job> &mjobs, hipStream_t stream) {
+  if (ln.tuples.ensure(tuples.size()) ||
+      ln.jobs.ensure(mjobs.size() * sizeof(kv::kv_job)))
+    return -2;
+  if (h2d_staged(ctx, ln.tuples.p, tuples.data(), tuples.size(), stream)) return -2;
+  if (mjobs.empty()) return 0;
+  if (h2d_staged(ctx, ln.jobs.p, mjobs.data(), mjobs.size() * sizeof(kv::kv_job),
+                 stream))
+    return -2;
+  hipLaunchKernelGGL(kv::kv_sighash_msg_kernel,
+                     dim3(((uint32_t)mjobs.size() + 255) / 256), dim3(256), 0, stream,
+                     ctx->vb.blob.as<const uint8_t>(),
+                     ctx->vb.subhashes.as<const uint8_t>(),
+                     ln.jobs.as<const kv::kv_job>(), (uint32_t)mjobs.size(),
+                     ln.tuples.as<uint8_t>(), ln.d.tuple_bytes, ln.d.msg_off);
+  return 0;
+}
+
+/* verify the lane's first n tuples into its bitmap and status */
+static int lane_verify(kv_ctx *ctx, VerifyLane &ln, size_t n, hipStream_t stream,
+                       bool *timed) {
+  if (ln.bitmap.ensure((n + 63) / 64 * 8) || ln.status.ensure(n)) return -2;
+  if (timed) tev_rec(ctx, ln.d.tev_verify, stream);
+  if (ln.d.ecdsa)
+    hipLaunchKernelGGL(kv::kv_ecdsa_verify_kernel, dim3(((uint32_t)n + 255) / 256),
+                       dim3(256), 0, stream, ln.tuples.as<const uint8_t>(),
+                       (unsigned long long)n, ln.bitmap.as<unsigned long long>(),
+                       ln.status.as<uint8_t>());
+  else if (launch_schnorr_verify(ctx, stream, ln.tuples.as<const uint8_t>(), n,
+                                 ln.bitmap.as<unsigned long long>(),
+                                 ln.status.as<uint8_t>()))
+    return -2;
+  if (timed) {
+    tev_rec(ctx, ln.d.tev_verify + 1, stream);
+    timed[ln.d.tev_verify / 2] = true;
+  }
+  return 0;
+}
+
+/* queue the readback of n statuses into the lane's pinned landing buffer;
+ * they are there once the caller has synchronised `stream` */
+static int lane_readback(VerifyLane &ln, size_t n, hipStream_t stream) {
+  if (ln.h_status.ensure(n)) return -2;
+  HIP_CHECK(hipMemcpyAsync(ln.h_status.p, ln.status.p, n, hipMemcpyDeviceToHost,
+                           stream));
+  return 0;
+}
+
+extern "C" int kv_sighash_batch(kv_ctx *ctx, const uint8_t *blob, size_t blob_len,
+                                const kv_sighash_job *jobs_in, size_t n,
+                                uint8_t *hashes_out) {
+  /* standalone sighash service over the blob (tests/parity). Jobs are split by
+   * kind — the assemble kernel uses different tuple strides for schnorr (128B)
+   * and ecdsa (132B). */
+  KV_ENTER(ctx);
+  ValidateBufs &vb = ctx->vb;
+  vector<HTx> txs;
+  if (parse_blob_host(blob, blob_len, txs) < 0) {
+    set_error("kv_sighash_batch: malformed blob");
+    return -1;
+  }
+  std::vector<kv::kv_job> jobs[2];
+  std::vector<size_t> slots(n); /* index in its lane's array */
+  for (size_t i = 0; i < n; i++) {
+    const kv_sighash_job &j = jobs_in[i];
+    if (j.tx_index >= txs.size() || j.input_index >= txs[j.tx_index].inputs.size()) {
+      set_error("kv_sighash_batch: bad job index");
+      return -1;
+    }
+    const HInput &in = txs[j.tx_index].inputs[j.input_index];
+    std::vector<kv::kv_job> &lane_jobs = jobs[j.ecdsa ? LANE_ECDSA : LANE_SCHNORR];
+    slots[i] = lane_jobs.size();
+    lane_jobs.push_back(
+        kv::kv_job{j.tx_index, in.rec_off, j.input_index, 0, 0, j.hash_type, j.ecdsa, 0});
+  }
+  uint32_t n_txs = (uint32_t)txs.size();
+  if (vb.blob.ensure(blob_len) || vb.subhashes.ensure((size_t)n_txs * 160))
+    return -2;
+  HIP_CHECK(hipMemcpyAsync(vb.blob.p, blob, blob_len, hipMemcpyHostToDevice,
+                           ctx->stream));
+  hipLaunchKernelGGL(kv::kv_tx_subhash_kernel, dim3((n_txs + 255) / 256), dim3(256), 0,
+                     ctx->stream, vb.blob.as<const uint8_t>(), n_txs,
+                     vb.subhashes.as<uint8_t>());
+  std::vector<uint8_t> tuples[2];
+  for (int k = 0; k < 2; k++) {
+    if (jobs[k].empty()) continue;
+    VerifyLane &ln = vb.lane[k];
+    tuples[k].resize(jobs[k].size() * ln.d.tuple_bytes);
+    int rc = lane_assemble(ctx, ln, jobs[k], ctx->stream, nullptr);
+    if (rc) return rc;
+    HIP_CHECK(hipMemcpyAsync(tuples[k].data(), ln.tuples.p, tuples[k].size(),
+                             hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < n; i++) {
+    const int k = jobs_in[i].ecdsa ? LANE_ECDSA : LANE_SCHNORR;
+    const LaneDesc &d = vb.lane[k].d;
+    memcpy(hashes_out + 32 * i,
+           tuples[k].data() + slots[i] * d.tuple_bytes + d.msg_off, 32);
+  }
+  return 0;
+}
+
 /* Enqueue the muhash element + reduce chain for txs with include[t] != 0 on
  * `stream`, fully async — the caller syncs the stream before reading outp.
  * The blob must already be resident in vb.blob. With no work the identity
@@ -1071,14 +1083,9 @@ static int enqueue_muhash(kv_ctx *ctx, const std::vector<HTx> &txs,
                           const uint8_t *include, uint64_t block_daa_score,
                           hipStream_t stream, bool *launched,
                           std::vector<kv::kv_elem_job> &jobs) {
-  ValidateBufs &vb = vb_of(ctx);
-  if (!ctx->h_mu_partial &&
-      hipHostMalloc(&ctx->h_mu_partial, 768) != hipSuccess) {
-    ctx->h_mu_partial = nullptr;
-    set_error("hipHostMalloc failed (muhash partial)");
-    return -2;
-  }
-  uint8_t *outp = ctx->h_mu_partial;
+  ValidateBufs &vb = ctx->vb;
+  if (ctx->h_mu_partial.ensure(768)) return -2;
+  uint8_t *outp = ctx->h_mu_partial.as<uint8_t>();
   jobs.clear();
   for (size_t t = 0; t < txs.size(); t++) {
     if (!include[t]) continue;
@@ -1117,17 +1124,17 @@ static int enqueue_muhash(kv_ctx *ctx, const std::vector<HTx> &txs,
   tev_rec(ctx, 10, stream);
   hipLaunchKernelGGL(kv::kv_muhash_element_kernel,
                      dim3(((uint32_t)n_all + 255) / 256), dim3(256), 0, stream,
-                     (const uint8_t *)vb.blob.p,
-                     (const kv::kv_elem_job *)vb.elem_jobs.p, (uint32_t)n_all,
-                     (uint64_t *)vb.elements.p);
+                     vb.blob.as<const uint8_t>(),
+                     vb.elem_jobs.as<const kv::kv_elem_job>(), (uint32_t)n_all,
+                     vb.elements.as<uint64_t>());
   /* reduce numerator then denominator halves down to one value each; the
    * stride schedule is pure host arithmetic, so the whole chain enqueues
    * without any device->host round trip */
   for (int half = 0; half < 2; half++) {
     size_t cnt = half == 0 ? n_num : n_den;
-    uint64_t *src = (uint64_t *)vb.elements.p + (half == 0 ? 0 : n_num * KVU_LIMBS);
-    uint64_t *pa = (uint64_t *)vb.partials_a.p;
-    uint64_t *pb = (uint64_t *)vb.partials_b.p;
+    uint64_t *src = vb.elements.as<uint64_t>() + (half == 0 ? 0 : n_num * KVU_LIMBS);
+    uint64_t *pa = vb.partials_a.as<uint64_t>();
+    uint64_t *pb = vb.partials_b.as<uint64_t>();
     if (cnt == 0) {
       memcpy(outp + half * 384, one.l, 384);
       continue;
@@ -1157,6 +1164,520 @@ static int enqueue_muhash(kv_ctx *ctx, const std::vector<HTx> &txs,
   return 0;
 }
 
+/* ---- validate_block_impl: the per-call state and its phases ---- */
+
+using vt_clock = std::chrono::steady_clock;
+
+/* host state of one verify lane during one validate call */
+struct LaneCall {
+  std::vector<kv::kv_job> jobs;   /* phase 1's jobs; after the cache probe, the misses */
+  std::vector<uint8_t> status;    /* one verdict per phase-1 job (resolve_input) */
+  std::vector<uint32_t> map;      /* cache on: miss k -> its phase-1 job index */
+  std::vector<kv_sig_key> keys;   /* cache on: one key per phase-1 job */
+};
+
+struct ValidateCall {
+  /* arguments */
+  const uint8_t *blob = nullptr;
+  size_t blob_len = 0;
+  uint64_t pov_daa_score = 0, block_daa_score = 0;
+  uint32_t flags = 0;
+  const int32_t *pre_codes = nullptr;
+  bool want_muhash = false;
+  /* parsed txs and per-tx results */
+  int n_txs = 0;
+  uint64_t sigop_units = 0;
+  vector<HTx> txs;
+  std::vector<int32_t> codes;
+  std::vector<uint64_t> fees;
+  std::vector<std::vector<InputPlan>> plans;
+  LaneCall lane[2];
+  bool use_cache = false;
+  /* device residency of this call's blob and subhashes */
+  bool blob_uploaded = false, subhash_done = false;
+  /* muhash: the include set of the enqueued chain */
+  bool mu_opt_launched = false;
+  std::vector<uint8_t> mu_inc;
+  std::vector<kv::kv_elem_job> mu_jobs;
+  bool tev_pair[6] = {}; /* which timing pairs of ctx->tev were recorded */
+  /* host timing points (KV_TIMING) */
+  vt_clock::time_point t_start, t_p1, t_enq, t_mu, t_rb, t_gpu, t_interp, t_resolve;
+};
+
+/* the call's blob into vb.blob, once per call: staged upload on ctx->stream,
+ * ev_blob recorded behind it */
+static int ensure_blob_resident(kv_ctx *ctx, ValidateCall &c) {
+  if (c.blob_uploaded) return 0;
+  if (ctx->vb.blob.ensure(c.blob_len)) return -2;
+  if (h2d_staged(ctx, ctx->vb.blob.p, c.blob, c.blob_len, ctx->stream)) return -2;
+  HIP_CHECK(hipEventRecord(ctx->ev_blob, ctx->stream));
+  c.blob_uploaded = true;
+  return 0;
+}
+
+/* the per-tx subhashes into vb.subhashes, once per call, on ctx->stream behind
+ * the blob; ev_sub recorded behind the kernel */
+static int ensure_subhashes(kv_ctx *ctx, ValidateCall &c) {
+  if (c.subhash_done) return 0;
+  if (ctx->vb.subhashes.ensure((size_t)c.n_txs * 160)) return -2;
+  tev_rec(ctx, 0);
+  hipLaunchKernelGGL(kv::kv_tx_subhash_kernel, dim3((c.n_txs + 255) / 256), dim3(256),
+                     0, ctx->stream, ctx->vb.blob.as<const uint8_t>(),
+                     (uint32_t)c.n_txs, ctx->vb.subhashes.as<uint8_t>());
+  tev_rec(ctx, 1);
+  c.tev_pair[0] = true;
+  HIP_CHECK(hipEventRecord(ctx->ev_sub, ctx->stream));
+  c.subhash_done = true;
+  return 0;
+}
+
+/* per-call scratch: timing events and record, pinned staging arena */
+static int validate_begin(kv_ctx *ctx, ValidateCall &c) {
+  c.sigop_units = ctx->params.mass_per_sig_op * KVH_UNITS_PER_GRAM;
+  tev_ensure(ctx);
+  ctx->last_timings = kv_validate_timings{};
+  /* generous upper bound: blob + verify jobs + muhash jobs */
+  size_t n_units = 0;
+  for (auto &tx : c.txs) n_units += tx.inputs.size() + tx.outputs.size();
+  return stage_reserve(ctx, c.blob_len + n_units * (sizeof(kv::kv_job) +
+                                                    sizeof(kv::kv_elem_job)) +
+                                (size_t)c.n_txs * 64 + 65536);
+}
+
+/* phase 1 for one tx: integer checks, fee, and one plan per input */
+static void phase1_tx(kv_ctx *ctx, ValidateCall &c, uint32_t t,
+                      std::vector<kv::kv_job> &sjobs, std::vector<kv::kv_job> &ejobs) {
+  HTx &tx = c.txs[t];
+  if (c.codes[t]) return;
+  if (h_is_coinbase(tx)) { /* coinbase never enters this path (utxo_validation.rs:297) */
+    c.codes[t] = KV_ERR_BAD_BLOB;
+    return;
+  }
+  int code = 0;
+  for (auto &in : tx.inputs)
+    if (in.utxo_is_coinbase &&
+        in.utxo_daa_score + ctx->params.coinbase_maturity > c.pov_daa_score) {
+      code = KV_ERR_IMMATURE_COINBASE;
+      break;
+    }
+  uint64_t total_in = 0, total_out = 0;
+  if (!code) {
+    for (auto &in : tx.inputs) {
+      if (total_in + in.utxo_amount < total_in) {
+        code = KV_ERR_INPUT_AMOUNT_OVERFLOW;
+        break;
+      }
+      total_in += in.utxo_amount;
+      if (total_in > KVH_MAX_SOMPI) {
+        code = KV_ERR_INPUT_AMOUNT_TOO_HIGH;
+        break;
+      }
+    }
+  }
+  if (!code) {
+    for (auto &o : tx.outputs) total_out += o.value;
+    if (total_in < total_out) code = KV_ERR_SPEND_TOO_HIGH;
+  }
+  if (!code && c.flags != KV_FLAGS_SKIP_MASS_CHECK) {
+    /* check_mass_commitment (tx_validation_in_utxo_context.rs:126-134) */
+    uint64_t calc = 0;
+    if (kvh_storage_mass(tx, false, &calc))
+      code = KV_ERR_MASS_INCOMPUTABLE;
+    else if (calc != tx.storage_mass)
+      code = KV_ERR_WRONG_MASS;
+  }
+  if (!code) {
+    for (auto &in : tx.inputs) {
+      if ((in.sequence & KVH_SEQ_DISABLED) == KVH_SEQ_DISABLED) continue;
+      int64_t lock = (int64_t)in.utxo_daa_score + (int64_t)(in.sequence & KVH_SEQ_MASK) - 1;
+      if (lock >= (int64_t)c.pov_daa_score) {
+        code = KV_ERR_SEQUENCE_LOCK;
+        break;
+      }
+    }
+  }
+  if (!code)
+    for (auto &o : tx.outputs)
+      if (o.has_covenant) {
+        code = KV_ERR_BAD_BLOB; /* covenants out of round-1 scope */
+        break;
+      }
+  c.codes[t] = code;
+  c.fees[t] = total_in - total_out;
+  if (code || c.flags == KV_FLAGS_SKIP_SCRIPT_CHECKS) return;
+  c.plans[t].reserve(tx.inputs.size());
+  for (uint32_t i = 0; i < tx.inputs.size(); i++)
+    c.plans[t].push_back(
+        classify_input(ctx, tx, tx.inputs[i], c.sigop_units, sjobs, ejobs, t, i));
+}
+
+/* phase 1: host integer checks + classification, fanned over the host cores
+ * (⇔ the reference's rayon pool) with per-chunk job lists so the GPU job
+ * order after concatenation equals the serial order */
+static void phase1_classify(kv_ctx *ctx, ValidateCall &c) {
+  const uint32_t n_txs = (uint32_t)c.n_txs;
+  c.plans.resize(n_txs);
+  c.codes.assign(n_txs, 0);
+  c.fees.assign(n_txs, 0);
+  if (c.pre_codes) c.codes.assign(c.pre_codes, c.pre_codes + n_txs);
+  unsigned P1T = kvh_threads(n_txs);
+  uint32_t p1_chunk = (n_txs + P1T - 1) / P1T;
+  std::vector<std::vector<kv::kv_job>> tl[2];
+  tl[LANE_SCHNORR].resize(P1T);
+  tl[LANE_ECDSA].resize(P1T);
+  if (P1T == 1) {
+    for (uint32_t t = 0; t < n_txs; t++)
+      phase1_tx(ctx, c, t, tl[LANE_SCHNORR][0], tl[LANE_ECDSA][0]);
+  } else {
+    KvhPool::inst().run([&](unsigned p) {
+      uint32_t lo = p * p1_chunk, hi = std::min(n_txs, lo + p1_chunk);
+      for (uint32_t t = lo; t < hi; t++)
+        phase1_tx(ctx, c, t, tl[LANE_SCHNORR][p], tl[LANE_ECDSA][p]);
+    });
+  }
+  /* concatenate chunk job lists (serial order preserved) and rebase the
+   * per-plan job indices by each chunk's offset */
+  std::vector<size_t> base[2];
+  for (int k = 0; k < 2; k++) {
+    size_t total = 0;
+    for (unsigned p = 0; p < P1T; p++) {
+      base[k].push_back(total);
+      total += tl[k][p].size();
+    }
+    c.lane[k].jobs.reserve(total);
+    for (unsigned p = 0; p < P1T; p++)
+      c.lane[k].jobs.insert(c.lane[k].jobs.end(), tl[k][p].begin(), tl[k][p].end());
+  }
+  if (P1T > 1)
+    for (uint32_t t = 0; t < n_txs; t++) {
+      unsigned p = t / p1_chunk;
+      for (auto &pl : c.plans[t]) {
+        if (pl.job >= 0)
+          pl.job += (int32_t)base[pl.ecdsa ? LANE_ECDSA : LANE_SCHNORR][p];
+        for (auto &ms : pl.msig_sigs)
+          if (ms.job0 >= 0) ms.job0 += (int32_t)base[LANE_SCHNORR][p];
+      }
+    }
+}
+
+/* phase 1.5: sig cache ⇔ TransactionValidator sig_cache (caches.rs:57-82).
+ * Key = blake2b-256(tx_id ‖ digest(all input entries) ‖ input_index ‖
+ * hash_type ‖ ecdsa ‖ sig ‖ pk): tx_id pins everything else the sighash
+ * commits to (it excludes sig scripts and utxo entries — those are keyed
+ * explicitly). Hits skip the GPU entirely; the job lists are compacted to
+ * the misses and statuses scattered back. */
+static void probe_sig_cache(kv_ctx *ctx, ValidateCall &c) {
+  for (auto &lc : c.lane) lc.status.resize(lc.jobs.size());
+  c.use_cache = ctx->params.sig_cache_size > 0 &&
+                c.lane[0].jobs.size() + c.lane[1].jobs.size() > 0;
+  if (!c.use_cache) return;
+  std::vector<uint8_t> need(c.n_txs, 0);
+  for (auto &lc : c.lane)
+    for (auto &j : lc.jobs) need[j.tx_index] = 1;
+  std::vector<std::array<uint8_t, 32>> ed(c.n_txs);
+  kvh_parallel_for((uint32_t)c.n_txs, [&](uint32_t t) {
+    if (!need[t]) return;
+    std::vector<uint8_t> buf;
+    buf.reserve(c.txs[t].inputs.size() * 60);
+    for (auto &in : c.txs[t].inputs) {
+      uint8_t tmp[22];
+      memcpy(tmp, &in.utxo_amount, 8);
+      memcpy(tmp + 8, &in.utxo_daa_score, 8);
+      tmp[16] = in.utxo_is_coinbase;
+      tmp[17] = in.utxo_has_cov;
+      memcpy(tmp + 18, &in.utxo_spk_version, 2);
+      uint16_t sl = (uint16_t)in.utxo_spk_len;
+      memcpy(tmp + 20, &sl, 2);
+      buf.insert(buf.end(), tmp, tmp + 22);
+      buf.insert(buf.end(), in.utxo_spk, in.utxo_spk + in.utxo_spk_len);
+    }
+    h_blake2b_keyed(nullptr, 0, buf.data(), buf.size(), ed[t].data());
+  });
+  for (auto &lc : c.lane) {
+    lc.keys.resize(lc.jobs.size());
+    kvh_parallel_for((uint32_t)lc.jobs.size(), [&](uint32_t i) {
+      const kv::kv_job &j = lc.jobs[i];
+      uint8_t buf[32 + 32 + 4 + 2 + 64 + 33];
+      size_t o = 0;
+      memcpy(buf + o, c.txs[j.tx_index].tx_id, 32);
+      o += 32;
+      memcpy(buf + o, ed[j.tx_index].data(), 32);
+      o += 32;
+      memcpy(buf + o, &j.input_index, 4);
+      o += 4;
+      buf[o++] = j.hash_type;
+      buf[o++] = j.ecdsa;
+      memcpy(buf + o, c.blob + j.sig_off, 64);
+      o += 64;
+      size_t pklen = j.ecdsa ? 33 : 32;
+      memcpy(buf + o, c.blob + j.pk_off, pklen);
+      o += pklen;
+      uint8_t h[32];
+      h_blake2b_keyed(nullptr, 0, buf, o, h);
+      memcpy(lc.keys[i].w, h, 32);
+    });
+    std::vector<kv::kv_job> miss;
+    miss.reserve(lc.jobs.size());
+    for (size_t i = 0; i < lc.jobs.size(); i++) {
+      auto it = ctx->sig_cache.find(lc.keys[i]);
+      if (it != ctx->sig_cache.end()) {
+        lc.status[i] = it->second;
+        ctx->cache_hits++;
+      } else {
+        ctx->cache_misses++;
+        lc.map.push_back((uint32_t)i);
+        miss.push_back(lc.jobs[i]);
+      }
+    }
+    lc.jobs.swap(miss);
+  }
+}
+
+/* phase 2: GPU — subhashes, sighash+tuple assembly, EC verify (cache
+ * misses only when the cache is on). Launches only; the readbacks follow the
+ * muhash enqueue. */
+static int enqueue_verify(kv_ctx *ctx, ValidateCall &c) {
+  const size_t ns = c.lane[LANE_SCHNORR].jobs.size();
+  const size_t ne = c.lane[LANE_ECDSA].jobs.size();
+  if (ns + ne == 0) return 0;
+  int rc = ensure_blob_resident(ctx, c);
+  if (!rc) rc = ensure_subhashes(ctx, c);
+  if (rc) return rc;
+  if (ns) {
+    VerifyLane &ln = ctx->vb.lane[LANE_SCHNORR];
+    rc = lane_assemble(ctx, ln, c.lane[LANE_SCHNORR].jobs, ctx->stream, c.tev_pair);
+    if (!rc) rc = lane_verify(ctx, ln, ns, ctx->stream, c.tev_pair);
+    if (rc) return rc;
+    ctx->last_timings.n_schnorr += ns;
+  }
+  if (ne) {
+    /* ecdsa chain on stream2: at block-path sizes both verify kernels are
+     * tiny latency-bound dispatches (a few hundred waves on a 2048-wave
+     * machine) — overlapping them hides the whole ecdsa chain behind the
+     * schnorr one */
+    VerifyLane &ln = ctx->vb.lane[LANE_ECDSA];
+    HIP_CHECK(hipStreamWaitEvent(ctx->stream2, ctx->ev_sub, 0));
+    rc = lane_assemble(ctx, ln, c.lane[LANE_ECDSA].jobs, ctx->stream2, c.tev_pair);
+    if (!rc) rc = lane_verify(ctx, ln, ne, ctx->stream2, c.tev_pair);
+    if (rc) return rc;
+    ctx->last_timings.n_ecdsa += ne;
+  }
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+/* optimistic muhash on stream3, overlapped with the verify chains: include
+ * every tx that passed the phase-1 integer checks. Phase 4 consumes the
+ * result when the final accept set matches (the overwhelmingly common
+ * case) and re-enqueues the exact set otherwise. */
+static int enqueue_optimistic_muhash(kv_ctx *ctx, ValidateCall &c) {
+  if (!c.want_muhash) return 0;
+  c.mu_inc.resize(c.n_txs);
+  for (int t = 0; t < c.n_txs; t++) c.mu_inc[t] = c.codes[t] == 0;
+  int rc = ensure_blob_resident(ctx, c);
+  if (rc) return rc;
+  HIP_CHECK(hipStreamWaitEvent(ctx->stream3, ctx->ev_blob, 0));
+  return enqueue_muhash(ctx, c.txs, c.mu_inc.data(), c.block_daa_score, ctx->stream3,
+                        &c.mu_opt_launched, c.mu_jobs);
+}
+
+/* status readbacks last (pinned, truly async) */
+static int enqueue_status_readbacks(kv_ctx *ctx, ValidateCall &c) {
+  hipStream_t streams[2] = {ctx->stream, ctx->stream2};
+  for (int k = 0; k < 2; k++)
+    if (size_t n = c.lane[k].jobs.size()) {
+      int rc = lane_readback(ctx->vb.lane[k], n, streams[k]);
+      if (rc) return rc;
+    }
+  return 0;
+}
+
+/* join the two verify streams */
+static int wait_verify(kv_ctx *ctx, ValidateCall &c) {
+  if (c.lane[0].jobs.size() + c.lane[1].jobs.size() == 0) return 0;
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream2));
+  return 0;
+}
+
+/* scatter GPU statuses back and remember fresh verdicts */
+static void collect_statuses(kv_ctx *ctx, ValidateCall &c) {
+  const size_t cap = (size_t)ctx->params.sig_cache_size;
+  for (int k = 0; k < 2; k++) {
+    LaneCall &lc = c.lane[k];
+    const size_t n = lc.jobs.size();
+    const uint8_t *gpu = ctx->vb.lane[k].h_status.as<const uint8_t>();
+    if (!c.use_cache) {
+      if (n) memcpy(lc.status.data(), gpu, n);
+      continue;
+    }
+    for (size_t i = 0; i < n; i++) {
+      lc.status[lc.map[i]] = gpu[i];
+      if (ctx->sig_cache.size() >= cap) ctx->sig_cache.erase(ctx->sig_cache.begin());
+      ctx->sig_cache.emplace(lc.keys[lc.map[i]], gpu[i]);
+      ctx->cache_insertions++;
+    }
+  }
+}
+
+/* phase 2.5: interpreter rounds — resolve suspended general-interpreter
+ * scripts over the GPU verify batch, one signature site per script per
+ * round (collect/replay protocol, kv_script_host.inc). Rounds =
+ * max signature-site depth over this block's non-template scripts (almost
+ * always 1); each round is one GPU batch over ALL suspended scripts, so
+ * the launch count does not scale with signature count. */
+static int interpreter_rounds(kv_ctx *ctx, ValidateCall &c) {
+  if (c.flags == KV_FLAGS_SKIP_SCRIPT_CHECKS) return 0;
+  ValidateBufs &vb = ctx->vb;
+  std::vector<std::pair<uint32_t, uint32_t>> islots;
+  for (int t = 0; t < c.n_txs; t++) {
+    if (c.codes[t]) continue;
+    for (uint32_t i = 0; i < c.plans[t].size(); i++)
+      if (c.plans[t][i].kind == PLAN_INTERP) islots.emplace_back((uint32_t)t, i);
+  }
+  std::vector<uint8_t> tup[2]; /* host-side tuple arrays per round */
+  while (!islots.empty()) {
+    tup[0].clear();
+    tup[1].clear();
+    std::vector<kv::kv_job> mjobs[2]; /* sighash-msg jobs */
+    struct ReqRef {
+      uint8_t ecdsa;
+      uint32_t idx;
+    };
+    std::vector<std::vector<ReqRef>> refs(islots.size());
+    for (size_t sl = 0; sl < islots.size(); sl++) {
+      uint32_t t = islots[sl].first, i = islots[sl].second;
+      InputPlan &pl = c.plans[t][i];
+      const HInput &in = c.txs[t].inputs[i];
+      for (const auto &rq : pl.pending) {
+        const uint8_t k = rq.ecdsa ? LANE_ECDSA : LANE_SCHNORR;
+        const LaneDesc &d = vb.lane[k].d;
+        uint32_t idx = (uint32_t)(tup[k].size() / d.tuple_bytes);
+        tup[k].resize(tup[k].size() + d.tuple_bytes);
+        uint8_t *tp = tup[k].data() + (size_t)idx * d.tuple_bytes;
+        memcpy(tp, rq.sig, 64);
+        memcpy(tp + 64, rq.pk, d.msg_off - 64); /* 32 B x-only, 33 B compressed */
+        if (rq.literal)
+          memcpy(tp + d.msg_off, rq.msg, 32);
+        else /* sig_off carries the tuple slot for the msg kernel */
+          mjobs[k].push_back(
+              kv::kv_job{t, in.rec_off, i, idx, 0, rq.hash_type, k, 0});
+        refs[sl].push_back({k, idx});
+      }
+    }
+    const size_t n_i[2] = {tup[0].size() / vb.lane[0].d.tuple_bytes,
+                           tup[1].size() / vb.lane[1].d.tuple_bytes};
+    if (n_i[0] + n_i[1] > 0) {
+      int rc = ensure_blob_resident(ctx, c);
+      if (!rc) rc = ensure_subhashes(ctx, c);
+      for (int k = 0; k < 2 && !rc; k++) {
+        if (!n_i[k]) continue;
+        VerifyLane &ln = vb.lane[k];
+        rc = lane_upload(ctx, ln, tup[k], mjobs[k], ctx->stream);
+        if (!rc) rc = lane_verify(ctx, ln, n_i[k], ctx->stream, nullptr);
+        if (!rc) rc = lane_readback(ln, n_i[k], ctx->stream);
+      }
+      if (rc) return rc;
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    const uint8_t *st[2] = {vb.lane[0].h_status.as<const uint8_t>(),
+                            vb.lane[1].h_status.as<const uint8_t>()};
+    /* feed statuses back as this site's memo entry and replay */
+    std::vector<uint8_t> survive(islots.size(), 0);
+    kvh_parallel_for((uint32_t)islots.size(), [&](uint32_t sl) {
+      uint32_t t = islots[sl].first, i = islots[sl].second;
+      InputPlan &pl = c.plans[t][i];
+      std::vector<uint8_t> entry(refs[sl].size());
+      for (size_t r = 0; r < refs[sl].size(); r++)
+        entry[r] = st[refs[sl][r].ecdsa][refs[sl][r].idx];
+      pl.memo.push_back(std::move(entry));
+      pl.pending.clear();
+      kvhost::KvsRunCtx rctx;
+      rctx.memo = &pl.memo;
+      rctx.pending = &pl.pending;
+      rctx.seqc_fn = ctx->seqc_fn;
+      rctx.seqc_user = ctx->seqc_user;
+      const HInput &in = c.txs[t].inputs[i];
+      int rc = kvh_run_input_script(c.txs[t], in, i, c.sigop_units, &rctx);
+      if (rc == kvhost::KVH_SCRIPT_SUSPEND) {
+        survive[sl] = 1;
+        return;
+      }
+      pl.kind = PLAN_NONE;
+      if (rc == kvhost::KVH_SCRIPT_DEFER)
+        pl.pre_code = KV_TX_DEFER_TO_CPU;
+      else if (rc != 0)
+        pl.pre_code = (in.sig_script_len == 0 ? KV_ERR_SIGNATURE_EMPTY_BASE
+                                              : KV_ERR_SIGNATURE_INVALID_BASE) +
+                      rc;
+      else
+        pl.pre_code = 0;
+    });
+    std::vector<std::pair<uint32_t, uint32_t>> next;
+    for (size_t sl = 0; sl < islots.size(); sl++)
+      if (survive[sl]) next.push_back(islots[sl]);
+    islots.swap(next);
+  }
+  return 0;
+}
+
+/* phase 3: resolution (first failing input wins, sequential semantics);
+ * read-only over the GPU statuses → fans over the host cores */
+static void resolve_codes(ValidateCall &c) {
+  kvh_parallel_for((uint32_t)c.n_txs, [&](uint32_t t) {
+    if (c.codes[t] || c.flags == KV_FLAGS_SKIP_SCRIPT_CHECKS) return;
+    for (uint32_t i = 0; i < c.txs[t].inputs.size(); i++) {
+      int code = resolve_input(c.plans[t][i], c.txs[t].inputs[i], c.sigop_units,
+                               c.lane[LANE_SCHNORR].status.data(),
+                               c.lane[LANE_ECDSA].status.data());
+      if (code) {
+        c.codes[t] = code;
+        break;
+      }
+    }
+  });
+}
+
+/* phase 4: consume the optimistic muhash, or re-enqueue over the exact
+ * accept set when some tx failed validation after the integer checks */
+static int finish_muhash(kv_ctx *ctx, ValidateCall &c, uint8_t *muhash_partial_out) {
+  if (!c.want_muhash) return 0;
+  bool match = true;
+  for (int t = 0; t < c.n_txs; t++)
+    if ((c.codes[t] == 0) != (c.mu_inc[t] != 0)) {
+      match = false;
+      break;
+    }
+  HIP_CHECK(hipStreamSynchronize(ctx->stream3)); /* optimistic writes done */
+  if (!match) {
+    for (int t = 0; t < c.n_txs; t++) c.mu_inc[t] = c.codes[t] == 0;
+    bool relaunched = false;
+    int rc = enqueue_muhash(ctx, c.txs, c.mu_inc.data(), c.block_daa_score,
+                            ctx->stream, &relaunched, c.mu_jobs);
+    if (rc) return rc;
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    c.tev_pair[5] = relaunched;
+  } else {
+    c.tev_pair[5] = c.mu_opt_launched;
+  }
+  memcpy(muhash_partial_out, ctx->h_mu_partial.p, 768);
+  return 0;
+}
+
+/* collect per-kernel timings (the stream is synchronized by now) */
+static int collect_timings(kv_ctx *ctx, const ValidateCall &c) {
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  kv_validate_timings &lt = ctx->last_timings;
+  if (c.tev_pair[0]) lt.subhash_ms = tev_ms(ctx, 0);
+  if (c.tev_pair[1]) lt.s_assemble_ms = tev_ms(ctx, 1);
+  if (c.tev_pair[2]) lt.e_assemble_ms = tev_ms(ctx, 2);
+  if (c.tev_pair[3]) lt.schnorr_ms = tev_ms(ctx, 3);
+  if (c.tev_pair[4]) lt.ecdsa_ms = tev_ms(ctx, 4);
+  if (c.tev_pair[5]) lt.muhash_ms = tev_ms(ctx, 5);
+  return 0;
+}
+
 /* caller holds ctx->mu; pre_codes (optional) pre-fails txs (e.g. missing
  * outpoints from the populate step) so they skip validation and muhash */
 static int validate_block_impl(kv_ctx *ctx, const uint8_t *blob, size_t blob_len,
@@ -1164,632 +1685,59 @@ static int validate_block_impl(kv_ctx *ctx, const uint8_t *blob, size_t blob_len
                                uint32_t flags, int32_t *tx_codes_out,
                                uint64_t *fees_out, uint8_t *muhash_partial_out,
                                const int32_t *pre_codes) {
-  vector<HTx> txs;
-  int n_txs = parse_blob_host(blob, blob_len, txs);
-  if (n_txs < 0) {
+  ValidateCall c;
+  c.blob = blob;
+  c.blob_len = blob_len;
+  c.pov_daa_score = pov_daa_score;
+  c.block_daa_score = block_daa_score;
+  c.flags = flags;
+  c.pre_codes = pre_codes;
+  c.want_muhash = muhash_partial_out != nullptr;
+  c.n_txs = parse_blob_host(blob, blob_len, c.txs);
+  if (c.n_txs < 0) {
     set_error("kv_validate_block: malformed blob");
     return -1;
   }
-  uint64_t sigop_units = ctx->params.mass_per_sig_op * KVH_UNITS_PER_GRAM;
-  ValidateBufs &vb = vb_of(ctx);
-  const bool kv_timing = getenv("KV_TIMING") != nullptr;
-  auto vt_now = []() { return std::chrono::steady_clock::now(); };
-  auto vt_ms = [](std::chrono::steady_clock::time_point a,
-                  std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double, std::milli>(b - a).count();
-  };
-  auto vt0 = vt_now();
-  tev_ensure(ctx);
-  bool tev_rec_pair[6] = {false, false, false, false, false, false};
-  ctx->last_timings = kv_validate_timings{};
-  {
-    /* generous upper bound: blob + verify jobs + muhash jobs */
-    size_t n_units = 0;
-    for (auto &tx : txs) n_units += tx.inputs.size() + tx.outputs.size();
-    if (stage_reserve(ctx, blob_len + n_units * (sizeof(kv::kv_job) +
-                                                 sizeof(kv::kv_elem_job)) +
-                               (size_t)n_txs * 64 + 65536))
-      return -2;
-  }
+  auto now = []() { return vt_clock::now(); };
+  int rc;
+  c.t_start = now();
+  if ((rc = validate_begin(ctx, c))) return rc;
+  phase1_classify(ctx, c);
+  c.t_p1 = now();
+  probe_sig_cache(ctx, c);
+  if ((rc = enqueue_verify(ctx, c))) return rc;
+  c.t_enq = now(); /* phase-2 launches done */
+  if ((rc = enqueue_optimistic_muhash(ctx, c))) return rc;
+  c.t_mu = now(); /* muhash enqueue done */
+  if ((rc = enqueue_status_readbacks(ctx, c))) return rc;
+  c.t_rb = now();
+  if ((rc = wait_verify(ctx, c))) return rc;
+  c.t_gpu = now();
+  collect_statuses(ctx, c);
+  if ((rc = interpreter_rounds(ctx, c))) return rc;
+  c.t_interp = now();
+  resolve_codes(c);
+  c.t_resolve = now();
+  if ((rc = finish_muhash(ctx, c, muhash_partial_out))) return rc;
+  if ((rc = collect_timings(ctx, c))) return rc;
 
-  /* phase 1: host integer checks + classification, fanned over the host cores
-   * (⇔ the reference's rayon pool) with per-chunk job lists so the GPU job
-   * order after concatenation equals the serial order */
-  std::vector<kv::kv_job> sjobs, ejobs;
-  std::vector<std::vector<InputPlan>> plans(n_txs);
-  std::vector<int32_t> codes(n_txs, 0);
-  std::vector<uint64_t> fees(n_txs, 0);
-  if (pre_codes)
-    for (int t = 0; t < n_txs; t++) codes[t] = pre_codes[t];
-  unsigned P1T = kvh_threads((uint32_t)n_txs);
-  uint32_t p1_chunk = ((uint32_t)n_txs + P1T - 1) / P1T;
-  std::vector<std::vector<kv::kv_job>> tl_s(P1T), tl_e(P1T);
-  auto phase1_tx = [&](uint32_t t, std::vector<kv::kv_job> &sjobs,
-                       std::vector<kv::kv_job> &ejobs) {
-    HTx &tx = txs[t];
-    if (codes[t]) return;
-    if (h_is_coinbase(tx)) { /* coinbase never enters this path (utxo_validation.rs:297) */
-      codes[t] = KV_ERR_BAD_BLOB;
-      return;
-    }
-    int code = 0;
-    for (auto &in : tx.inputs)
-      if (in.utxo_is_coinbase &&
-          in.utxo_daa_score + ctx->params.coinbase_maturity > pov_daa_score) {
-        code = KV_ERR_IMMATURE_COINBASE;
-        break;
-      }
-    uint64_t total_in = 0, total_out = 0;
-    if (!code) {
-      for (auto &in : tx.inputs) {
-        if (total_in + in.utxo_amount < total_in) {
-          code = KV_ERR_INPUT_AMOUNT_OVERFLOW;
-          break;
-        }
-        total_in += in.utxo_amount;
-        if (total_in > KVH_MAX_SOMPI) {
-          code = KV_ERR_INPUT_AMOUNT_TOO_HIGH;
-          break;
-        }
-      }
-    }
-    if (!code) {
-      for (auto &o : tx.outputs) total_out += o.value;
-      if (total_in < total_out) code = KV_ERR_SPEND_TOO_HIGH;
-    }
-    if (!code && flags != KV_FLAGS_SKIP_MASS_CHECK) {
-      /* check_mass_commitment (tx_validation_in_utxo_context.rs:126-134) */
-      uint64_t calc = 0;
-      if (kvh_storage_mass(tx, false, &calc))
-        code = KV_ERR_MASS_INCOMPUTABLE;
-      else if (calc != tx.storage_mass)
-        code = KV_ERR_WRONG_MASS;
-    }
-    if (!code) {
-      for (auto &in : tx.inputs) {
-        if ((in.sequence & KVH_SEQ_DISABLED) == KVH_SEQ_DISABLED) continue;
-        int64_t lock = (int64_t)in.utxo_daa_score + (int64_t)(in.sequence & KVH_SEQ_MASK) - 1;
-        if (lock >= (int64_t)pov_daa_score) {
-          code = KV_ERR_SEQUENCE_LOCK;
-          break;
-        }
-      }
-    }
-    if (!code)
-      for (auto &o : tx.outputs)
-        if (o.has_covenant) {
-          code = KV_ERR_BAD_BLOB; /* covenants out of round-1 scope */
-          break;
-        }
-    codes[t] = code;
-    fees[t] = total_in - total_out;
-    if (code || flags == KV_FLAGS_SKIP_SCRIPT_CHECKS) return;
-    plans[t].reserve(tx.inputs.size());
-    for (uint32_t i = 0; i < tx.inputs.size(); i++)
-      plans[t].push_back(
-          classify_input(ctx, tx, tx.inputs[i], sigop_units, sjobs, ejobs, t, i));
-  };
-  {
-    if (P1T == 1) {
-      for (uint32_t t = 0; t < (uint32_t)n_txs; t++)
-        phase1_tx(t, tl_s[0], tl_e[0]);
-    } else {
-      KvhPool::inst().run([&](unsigned k) {
-        uint32_t lo = k * p1_chunk,
-                 hi = std::min((uint32_t)n_txs, lo + p1_chunk);
-        for (uint32_t t = lo; t < hi; t++) phase1_tx(t, tl_s[k], tl_e[k]);
-      });
-    }
-    /* concatenate chunk job lists (serial order preserved) and rebase the
-     * per-plan job indices by each chunk's offset */
-    std::vector<size_t> s_base(P1T, 0), e_base(P1T, 0);
-    size_t sa = 0, ea = 0;
-    for (unsigned k = 0; k < P1T; k++) {
-      s_base[k] = sa;
-      e_base[k] = ea;
-      sa += tl_s[k].size();
-      ea += tl_e[k].size();
-    }
-    sjobs.reserve(sa);
-    ejobs.reserve(ea);
-    for (unsigned k = 0; k < P1T; k++) {
-      sjobs.insert(sjobs.end(), tl_s[k].begin(), tl_s[k].end());
-      ejobs.insert(ejobs.end(), tl_e[k].begin(), tl_e[k].end());
-    }
-    if (P1T > 1)
-      for (int t = 0; t < n_txs; t++) {
-        unsigned k = (uint32_t)t / p1_chunk;
-        for (auto &pl : plans[t]) {
-          if (pl.job >= 0) pl.job += (int32_t)(pl.ecdsa ? e_base[k] : s_base[k]);
-          for (auto &ms : pl.msig_sigs)
-            if (ms.job0 >= 0) ms.job0 += (int32_t)s_base[k];
-        }
-      }
-  }
-
-  auto vt1 = vt_now();
-  auto vt1a = vt1, vt1b = vt1, vt1c = vt1;
-
-  /* phase 1.5: sig cache ⇔ TransactionValidator sig_cache (caches.rs:57-82).
-   * Key = blake2b-256(tx_id ‖ digest(all input entries) ‖ input_index ‖
-   * hash_type ‖ ecdsa ‖ sig ‖ pk): tx_id pins everything else the sighash
-   * commits to (it excludes sig scripts and utxo entries — those are keyed
-   * explicitly). Hits skip the GPU entirely; the job lists are compacted to
-   * the misses and statuses scattered back. */
-  size_t ns_all = sjobs.size(), ne_all = ejobs.size();
-  std::vector<uint8_t> s_status(ns_all), e_status(ne_all);
-  std::vector<uint32_t> s_map, e_map;
-  std::vector<kv_sig_key> s_keys, e_keys;
-  bool use_cache = ctx->params.sig_cache_size > 0 && ns_all + ne_all > 0;
-  if (use_cache) {
-    std::vector<uint8_t> need(n_txs, 0);
-    for (auto &j : sjobs) need[j.tx_index] = 1;
-    for (auto &j : ejobs) need[j.tx_index] = 1;
-    std::vector<std::array<uint8_t, 32>> ed(n_txs);
-    kvh_parallel_for((uint32_t)n_txs, [&](uint32_t t) {
-      if (!need[t]) return;
-      std::vector<uint8_t> buf;
-      buf.reserve(txs[t].inputs.size() * 60);
-      for (auto &in : txs[t].inputs) {
-        uint8_t tmp[22];
-        memcpy(tmp, &in.utxo_amount, 8);
-        memcpy(tmp + 8, &in.utxo_daa_score, 8);
-        tmp[16] = in.utxo_is_coinbase;
-        tmp[17] = in.utxo_has_cov;
-        memcpy(tmp + 18, &in.utxo_spk_version, 2);
-        uint16_t sl = (uint16_t)in.utxo_spk_len;
-        memcpy(tmp + 20, &sl, 2);
-        buf.insert(buf.end(), tmp, tmp + 22);
-        buf.insert(buf.end(), in.utxo_spk, in.utxo_spk + in.utxo_spk_len);
-      }
-      h_blake2b_keyed(nullptr, 0, buf.data(), buf.size(), ed[t].data());
-    });
-    auto keygen = [&](const std::vector<kv::kv_job> &jobs,
-                      std::vector<kv_sig_key> &keys) {
-      keys.resize(jobs.size());
-      kvh_parallel_for((uint32_t)jobs.size(), [&](uint32_t i) {
-        const kv::kv_job &j = jobs[i];
-        uint8_t buf[32 + 32 + 4 + 2 + 64 + 33];
-        size_t o = 0;
-        memcpy(buf + o, txs[j.tx_index].tx_id, 32);
-        o += 32;
-        memcpy(buf + o, ed[j.tx_index].data(), 32);
-        o += 32;
-        memcpy(buf + o, &j.input_index, 4);
-        o += 4;
-        buf[o++] = j.hash_type;
-        buf[o++] = j.ecdsa;
-        memcpy(buf + o, blob + j.sig_off, 64);
-        o += 64;
-        size_t pklen = j.ecdsa ? 33 : 32;
-        memcpy(buf + o, blob + j.pk_off, pklen);
-        o += pklen;
-        uint8_t h[32];
-        h_blake2b_keyed(nullptr, 0, buf, o, h);
-        memcpy(keys[i].w, h, 32);
-      });
+  for (int t = 0; t < c.n_txs; t++)
+    if (c.codes[t]) c.fees[t] = 0; /* fee defined only for accepted txs */
+  memcpy(tx_codes_out, c.codes.data(), (size_t)c.n_txs * 4);
+  memcpy(fees_out, c.fees.data(), (size_t)c.n_txs * 8);
+  if (getenv("KV_TIMING")) {
+    auto ms = [](vt_clock::time_point a, vt_clock::time_point b) {
+      return std::chrono::duration<double, std::milli>(b - a).count();
     };
-    keygen(sjobs, s_keys);
-    keygen(ejobs, e_keys);
-    auto probe = [&](std::vector<kv::kv_job> &jobs,
-                     const std::vector<kv_sig_key> &keys,
-                     std::vector<uint8_t> &status, std::vector<uint32_t> &map) {
-      std::vector<kv::kv_job> miss;
-      miss.reserve(jobs.size());
-      for (size_t i = 0; i < jobs.size(); i++) {
-        auto it = ctx->sig_cache.find(keys[i]);
-        if (it != ctx->sig_cache.end()) {
-          status[i] = it->second;
-          ctx->cache_hits++;
-        } else {
-          ctx->cache_misses++;
-          map.push_back((uint32_t)i);
-          miss.push_back(jobs[i]);
-        }
-      }
-      jobs.swap(miss);
-    };
-    probe(sjobs, s_keys, s_status, s_map);
-    probe(ejobs, e_keys, e_status, e_map);
-  }
-
-  /* phase 2: GPU — subhashes, sighash+tuple assembly, EC verify (cache
-   * misses only when the cache is on) */
-  size_t ns = sjobs.size(), ne = ejobs.size();
-  std::vector<uint8_t> s_gpu(ns), e_gpu(ne);
-  bool blob_uploaded = false, subhash_done = false;
-  if (ns + ne > 0) {
-    if (vb.blob.ensure(blob_len) || vb.subhashes.ensure((size_t)n_txs * 160))
-      return -2;
-    if (h2d_staged(ctx, vb.blob.p, blob, blob_len, ctx->stream)) return -2;
-    HIP_CHECK(hipEventRecord(ctx->ev_blob, ctx->stream));
-    blob_uploaded = true;
-    tev_rec(ctx, 0);
-    hipLaunchKernelGGL(kv::kv_tx_subhash_kernel, dim3((n_txs + 255) / 256), dim3(256),
-                       0, ctx->stream, (const uint8_t *)vb.blob.p, (uint32_t)n_txs,
-                       (uint8_t *)vb.subhashes.p);
-    tev_rec(ctx, 1);
-    tev_rec_pair[0] = true;
-    HIP_CHECK(hipEventRecord(ctx->ev_sub, ctx->stream));
-    subhash_done = true;
-    if (ns) {
-      if (vb.s_jobs.ensure(ns * sizeof(kv::kv_job)) ||
-          vb.s_tuples.ensure(ns * 128) || vb.s_bitmap.ensure((ns + 63) / 64 * 8) ||
-          vb.s_status.ensure(ns))
-        return -2;
-      if (h2d_staged(ctx, vb.s_jobs.p, sjobs.data(), ns * sizeof(kv::kv_job),
-                     ctx->stream))
-        return -2;
-      tev_rec(ctx, 2);
-      hipLaunchKernelGGL(kv::kv_sighash_assemble_kernel,
-                         dim3(((uint32_t)ns + 255) / 256), dim3(256), 0, ctx->stream,
-                         (const uint8_t *)vb.blob.p, (const uint8_t *)vb.subhashes.p,
-                         (const kv::kv_job *)vb.s_jobs.p, (uint32_t)ns,
-                         (uint8_t *)vb.s_tuples.p, (uint8_t *)vb.s_tuples.p);
-      tev_rec(ctx, 3);
-      tev_rec_pair[1] = true;
-      tev_rec(ctx, 6);
-      if (launch_schnorr_verify(ctx, (const uint8_t *)vb.s_tuples.p, ns,
-                                (unsigned long long *)vb.s_bitmap.p,
-                                (uint8_t *)vb.s_status.p))
-        return -2;
-      tev_rec(ctx, 7);
-      tev_rec_pair[3] = true;
-      ctx->last_timings.n_schnorr += ns;
-    }
-    if (ne) {
-      /* ecdsa chain on stream2: at block-path sizes both verify kernels are
-       * tiny latency-bound dispatches (a few hundred waves on a 2048-wave
-       * machine) — overlapping them hides the whole ecdsa chain behind the
-       * schnorr one */
-      if (vb.e_jobs.ensure(ne * sizeof(kv::kv_job)) ||
-          vb.e_tuples.ensure(ne * 132) || vb.e_bitmap.ensure((ne + 63) / 64 * 8) ||
-          vb.e_status.ensure(ne))
-        return -2;
-      HIP_CHECK(hipStreamWaitEvent(ctx->stream2, ctx->ev_sub, 0));
-      if (h2d_staged(ctx, vb.e_jobs.p, ejobs.data(), ne * sizeof(kv::kv_job),
-                     ctx->stream2))
-        return -2;
-      tev_rec(ctx, 4, ctx->stream2);
-      hipLaunchKernelGGL(kv::kv_sighash_assemble_kernel,
-                         dim3(((uint32_t)ne + 255) / 256), dim3(256), 0, ctx->stream2,
-                         (const uint8_t *)vb.blob.p, (const uint8_t *)vb.subhashes.p,
-                         (const kv::kv_job *)vb.e_jobs.p, (uint32_t)ne,
-                         (uint8_t *)vb.e_tuples.p, (uint8_t *)vb.e_tuples.p);
-      tev_rec(ctx, 5, ctx->stream2);
-      tev_rec_pair[2] = true;
-      tev_rec(ctx, 8, ctx->stream2);
-      hipLaunchKernelGGL(kv::kv_ecdsa_verify_kernel, dim3(((uint32_t)ne + 255) / 256),
-                         dim3(256), 0, ctx->stream2, (const uint8_t *)vb.e_tuples.p,
-                         (unsigned long long)ne, (unsigned long long *)vb.e_bitmap.p,
-                         (uint8_t *)vb.e_status.p);
-      tev_rec(ctx, 9, ctx->stream2);
-      tev_rec_pair[4] = true;
-      ctx->last_timings.n_ecdsa += ne;
-    }
-    HIP_CHECK(hipGetLastError());
-  }
-  vt1a = vt_now(); /* phase-2 launches done */
-
-  /* optimistic muhash on stream3, overlapped with the verify chains: include
-   * every tx that passed the phase-1 integer checks. Phase 4 consumes the
-   * result when the final accept set matches (the overwhelmingly common
-   * case) and re-enqueues the exact set otherwise. */
-  bool mu_opt_launched = false;
-  std::vector<uint8_t> mu_inc;
-  std::vector<kv::kv_elem_job> mu_jobs;
-  if (muhash_partial_out) {
-    mu_inc.resize(n_txs);
-    for (int t = 0; t < n_txs; t++) mu_inc[t] = codes[t] == 0;
-    if (!blob_uploaded) {
-      if (vb.blob.ensure(blob_len)) return -2;
-      if (h2d_staged(ctx, vb.blob.p, blob, blob_len, ctx->stream)) return -2;
-      HIP_CHECK(hipEventRecord(ctx->ev_blob, ctx->stream));
-      blob_uploaded = true;
-    }
-    HIP_CHECK(hipStreamWaitEvent(ctx->stream3, ctx->ev_blob, 0));
-    int mrc = enqueue_muhash(ctx, txs, mu_inc.data(), block_daa_score, ctx->stream3,
-                             &mu_opt_launched, mu_jobs);
-    if (mrc) return mrc;
-  }
-  vt1b = vt_now(); /* muhash enqueue done */
-  /* status readbacks last (pinned, truly async), then join the streams */
-  if (ns) {
-    if (ctx->h_s_cap < ns) {
-      if (ctx->h_s_status) (void)hipHostFree(ctx->h_s_status);
-      size_t nc = ns + ns / 2 + 256;
-      if (hipHostMalloc(&ctx->h_s_status, nc) != hipSuccess) {
-        ctx->h_s_status = nullptr;
-        ctx->h_s_cap = 0;
-        set_error("hipHostMalloc failed (status)");
-        return -2;
-      }
-      ctx->h_s_cap = nc;
-    }
-    HIP_CHECK(hipMemcpyAsync(ctx->h_s_status, vb.s_status.p, ns,
-                             hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (ne) {
-    if (ctx->h_e_cap < ne) {
-      if (ctx->h_e_status) (void)hipHostFree(ctx->h_e_status);
-      size_t nc = ne + ne / 2 + 256;
-      if (hipHostMalloc(&ctx->h_e_status, nc) != hipSuccess) {
-        ctx->h_e_status = nullptr;
-        ctx->h_e_cap = 0;
-        set_error("hipHostMalloc failed (status)");
-        return -2;
-      }
-      ctx->h_e_cap = nc;
-    }
-    HIP_CHECK(hipMemcpyAsync(ctx->h_e_status, vb.e_status.p, ne,
-                             hipMemcpyDeviceToHost, ctx->stream2));
-  }
-  auto vt2 = vt_now();
-  if (ns + ne > 0) {
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream2));
-    if (ns) memcpy(s_gpu.data(), ctx->h_s_status, ns);
-    if (ne) memcpy(e_gpu.data(), ctx->h_e_status, ne);
-  }
-  auto vt3 = vt_now();
-
-  /* scatter GPU statuses back and remember fresh verdicts */
-  if (use_cache) {
-    size_t cap = (size_t)ctx->params.sig_cache_size;
-    for (size_t k = 0; k < ns; k++) {
-      s_status[s_map[k]] = s_gpu[k];
-      if (ctx->sig_cache.size() >= cap)
-        ctx->sig_cache.erase(ctx->sig_cache.begin());
-      ctx->sig_cache.emplace(s_keys[s_map[k]], s_gpu[k]);
-      ctx->cache_insertions++;
-    }
-    for (size_t k = 0; k < ne; k++) {
-      e_status[e_map[k]] = e_gpu[k];
-      if (ctx->sig_cache.size() >= cap)
-        ctx->sig_cache.erase(ctx->sig_cache.begin());
-      ctx->sig_cache.emplace(e_keys[e_map[k]], e_gpu[k]);
-      ctx->cache_insertions++;
-    }
-  } else {
-    s_status.swap(s_gpu);
-    e_status.swap(e_gpu);
-  }
-
-  /* phase 2.5: interpreter rounds — resolve suspended general-interpreter
-   * scripts over the GPU verify batch, one signature site per script per
-   * round (collect/replay protocol, kv_script_host.inc). Rounds =
-   * max signature-site depth over this block's non-template scripts (almost
-   * always 1); each round is one GPU batch over ALL suspended scripts, so
-   * the launch count does not scale with signature count. */
-  if (flags != KV_FLAGS_SKIP_SCRIPT_CHECKS) {
-    std::vector<std::pair<uint32_t, uint32_t>> islots;
-    for (int t = 0; t < n_txs; t++) {
-      if (codes[t]) continue;
-      for (uint32_t i = 0; i < plans[t].size(); i++)
-        if (plans[t][i].kind == PLAN_INTERP) islots.emplace_back((uint32_t)t, i);
-    }
-    std::vector<uint8_t> st_h, et_h; /* host-side tuple arrays per round */
-    while (!islots.empty()) {
-      st_h.clear();
-      et_h.clear();
-      std::vector<kv::kv_job> mjobs_s, mjobs_e; /* sighash-msg jobs */
-      struct ReqRef {
-        uint8_t ecdsa;
-        uint32_t idx;
-      };
-      std::vector<std::vector<ReqRef>> refs(islots.size());
-      for (size_t sl = 0; sl < islots.size(); sl++) {
-        uint32_t t = islots[sl].first, i = islots[sl].second;
-        InputPlan &pl = plans[t][i];
-        const HInput &in = txs[t].inputs[i];
-        for (const auto &rq : pl.pending) {
-          if (!rq.ecdsa) {
-            uint32_t idx = (uint32_t)(st_h.size() / 128);
-            st_h.resize(st_h.size() + 128);
-            uint8_t *tp = st_h.data() + (size_t)idx * 128;
-            memcpy(tp, rq.sig, 64);
-            memcpy(tp + 64, rq.pk, 32);
-            if (rq.literal)
-              memcpy(tp + 96, rq.msg, 32);
-            else /* sig_off carries the tuple slot for the msg kernel */
-              mjobs_s.push_back(
-                  kv::kv_job{t, in.rec_off, i, idx, 0, rq.hash_type, 0, 0});
-            refs[sl].push_back({0, idx});
-          } else {
-            uint32_t idx = (uint32_t)(et_h.size() / 132);
-            et_h.resize(et_h.size() + 132);
-            uint8_t *tp = et_h.data() + (size_t)idx * 132;
-            memcpy(tp, rq.sig, 64);
-            memcpy(tp + 64, rq.pk, 33);
-            if (rq.literal)
-              memcpy(tp + 97, rq.msg, 32);
-            else
-              mjobs_e.push_back(
-                  kv::kv_job{t, in.rec_off, i, idx, 0, rq.hash_type, 1, 0});
-            refs[sl].push_back({1, idx});
-          }
-        }
-      }
-      size_t ns_i = st_h.size() / 128, ne_i = et_h.size() / 132;
-      std::vector<uint8_t> s_st(ns_i), e_st(ne_i);
-      if (ns_i + ne_i > 0) {
-        if (!blob_uploaded) {
-          if (vb.blob.ensure(blob_len)) return -2;
-          HIP_CHECK(hipMemcpyAsync(vb.blob.p, blob, blob_len,
-                                   hipMemcpyHostToDevice, ctx->stream));
-          blob_uploaded = true;
-        }
-        if (!subhash_done) {
-          if (vb.subhashes.ensure((size_t)n_txs * 160)) return -2;
-          hipLaunchKernelGGL(kv::kv_tx_subhash_kernel, dim3((n_txs + 255) / 256),
-                             dim3(256), 0, ctx->stream,
-                             (const uint8_t *)vb.blob.p, (uint32_t)n_txs,
-                             (uint8_t *)vb.subhashes.p);
-          subhash_done = true;
-        }
-        if (ns_i) {
-          if (vb.s_tuples.ensure(st_h.size()) ||
-              vb.s_bitmap.ensure((ns_i + 63) / 64 * 8) ||
-              vb.s_status.ensure(ns_i) ||
-              (!mjobs_s.empty() &&
-               vb.s_jobs.ensure(mjobs_s.size() * sizeof(kv::kv_job))))
-            return -2;
-          HIP_CHECK(hipMemcpyAsync(vb.s_tuples.p, st_h.data(), st_h.size(),
-                                   hipMemcpyHostToDevice, ctx->stream));
-          if (!mjobs_s.empty()) {
-            HIP_CHECK(hipMemcpyAsync(vb.s_jobs.p, mjobs_s.data(),
-                                     mjobs_s.size() * sizeof(kv::kv_job),
-                                     hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(kv::kv_sighash_msg_kernel,
-                               dim3(((uint32_t)mjobs_s.size() + 255) / 256),
-                               dim3(256), 0, ctx->stream,
-                               (const uint8_t *)vb.blob.p,
-                               (const uint8_t *)vb.subhashes.p,
-                               (const kv::kv_job *)vb.s_jobs.p,
-                               (uint32_t)mjobs_s.size(),
-                               (uint8_t *)vb.s_tuples.p, 128u, 96u);
-          }
-          if (launch_schnorr_verify(ctx, (const uint8_t *)vb.s_tuples.p, ns_i,
-                                    (unsigned long long *)vb.s_bitmap.p,
-                                    (uint8_t *)vb.s_status.p))
-            return -2;
-          HIP_CHECK(hipMemcpyAsync(s_st.data(), vb.s_status.p, ns_i,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (ne_i) {
-          if (vb.e_tuples.ensure(et_h.size()) ||
-              vb.e_bitmap.ensure((ne_i + 63) / 64 * 8) ||
-              vb.e_status.ensure(ne_i) ||
-              (!mjobs_e.empty() &&
-               vb.e_jobs.ensure(mjobs_e.size() * sizeof(kv::kv_job))))
-            return -2;
-          HIP_CHECK(hipMemcpyAsync(vb.e_tuples.p, et_h.data(), et_h.size(),
-                                   hipMemcpyHostToDevice, ctx->stream));
-          if (!mjobs_e.empty()) {
-            HIP_CHECK(hipMemcpyAsync(vb.e_jobs.p, mjobs_e.data(),
-                                     mjobs_e.size() * sizeof(kv::kv_job),
-                                     hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(kv::kv_sighash_msg_kernel,
-                               dim3(((uint32_t)mjobs_e.size() + 255) / 256),
-                               dim3(256), 0, ctx->stream,
-                               (const uint8_t *)vb.blob.p,
-                               (const uint8_t *)vb.subhashes.p,
-                               (const kv::kv_job *)vb.e_jobs.p,
-                               (uint32_t)mjobs_e.size(),
-                               (uint8_t *)vb.e_tuples.p, 132u, 97u);
-          }
-          hipLaunchKernelGGL(kv::kv_ecdsa_verify_kernel,
-                             dim3(((uint32_t)ne_i + 255) / 256), dim3(256), 0,
-                             ctx->stream, (const uint8_t *)vb.e_tuples.p,
-                             (unsigned long long)ne_i,
-                             (unsigned long long *)vb.e_bitmap.p,
-                             (uint8_t *)vb.e_status.p);
-          HIP_CHECK(hipMemcpyAsync(e_st.data(), vb.e_status.p, ne_i,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      }
-      /* feed statuses back as this site's memo entry and replay */
-      std::vector<uint8_t> survive(islots.size(), 0);
-      kvh_parallel_for((uint32_t)islots.size(), [&](uint32_t sl) {
-        uint32_t t = islots[sl].first, i = islots[sl].second;
-        InputPlan &pl = plans[t][i];
-        std::vector<uint8_t> entry(refs[sl].size());
-        for (size_t r = 0; r < refs[sl].size(); r++)
-          entry[r] = refs[sl][r].ecdsa ? e_st[refs[sl][r].idx]
-                                       : s_st[refs[sl][r].idx];
-        pl.memo.push_back(std::move(entry));
-        pl.pending.clear();
-        kvhost::KvsRunCtx rctx;
-        rctx.memo = &pl.memo;
-        rctx.pending = &pl.pending;
-        rctx.seqc_fn = ctx->seqc_fn;
-        rctx.seqc_user = ctx->seqc_user;
-        const HInput &in = txs[t].inputs[i];
-        int rc = kvh_run_input_script(txs[t], in, i, sigop_units, &rctx);
-        if (rc == kvhost::KVH_SCRIPT_SUSPEND) {
-          survive[sl] = 1;
-          return;
-        }
-        pl.kind = PLAN_NONE;
-        if (rc == kvhost::KVH_SCRIPT_DEFER)
-          pl.pre_code = KV_TX_DEFER_TO_CPU;
-        else if (rc != 0)
-          pl.pre_code = (in.sig_script_len == 0 ? KV_ERR_SIGNATURE_EMPTY_BASE
-                                                : KV_ERR_SIGNATURE_INVALID_BASE) +
-                        rc;
-        else
-          pl.pre_code = 0;
-      });
-      std::vector<std::pair<uint32_t, uint32_t>> next;
-      for (size_t sl = 0; sl < islots.size(); sl++)
-        if (survive[sl]) next.push_back(islots[sl]);
-      islots.swap(next);
-    }
-  }
-
-  auto vt4 = vt_now();
-  /* phase 3: resolution (first failing input wins, sequential semantics);
-   * read-only over the GPU statuses → fans over the host cores */
-  kvh_parallel_for((uint32_t)n_txs, [&](uint32_t t) {
-    if (codes[t] || flags == KV_FLAGS_SKIP_SCRIPT_CHECKS) return;
-    for (uint32_t i = 0; i < txs[t].inputs.size(); i++) {
-      int c = resolve_input(plans[t][i], txs[t].inputs[i], sigop_units,
-                            s_status.data(), e_status.data());
-      if (c) {
-        codes[t] = c;
-        break;
-      }
-    }
-  });
-
-  auto vt5 = vt_now();
-  /* phase 4: consume the optimistic muhash, or re-enqueue over the exact
-   * accept set when some tx failed validation after the integer checks */
-  if (muhash_partial_out) {
-    bool match = true;
-    for (int t = 0; t < n_txs; t++)
-      if ((codes[t] == 0) != (mu_inc[t] != 0)) {
-        match = false;
-        break;
-      }
-    HIP_CHECK(hipStreamSynchronize(ctx->stream3)); /* optimistic writes done */
-    if (!match) {
-      for (int t = 0; t < n_txs; t++) mu_inc[t] = codes[t] == 0;
-      bool relaunched = false;
-      int mrc = enqueue_muhash(ctx, txs, mu_inc.data(), block_daa_score,
-                               ctx->stream, &relaunched, mu_jobs);
-      if (mrc) return mrc;
-      HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      tev_rec_pair[5] = relaunched;
-    } else {
-      tev_rec_pair[5] = mu_opt_launched;
-    }
-    memcpy(muhash_partial_out, ctx->h_mu_partial, 768);
-  }
-
-  /* collect per-kernel timings (the stream is synchronized by now) */
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (tev_rec_pair[0]) ctx->last_timings.subhash_ms = tev_ms(ctx, 0);
-  if (tev_rec_pair[1]) ctx->last_timings.s_assemble_ms = tev_ms(ctx, 1);
-  if (tev_rec_pair[2]) ctx->last_timings.e_assemble_ms = tev_ms(ctx, 2);
-  if (tev_rec_pair[3]) ctx->last_timings.schnorr_ms = tev_ms(ctx, 3);
-  if (tev_rec_pair[4]) ctx->last_timings.ecdsa_ms = tev_ms(ctx, 4);
-  if (tev_rec_pair[5]) ctx->last_timings.muhash_ms = tev_ms(ctx, 5);
-
-  for (int t = 0; t < n_txs; t++)
-    if (codes[t]) fees[t] = 0; /* fee defined only for accepted txs */
-  memcpy(tx_codes_out, codes.data(), (size_t)n_txs * 4);
-  memcpy(fees_out, fees.data(), (size_t)n_txs * 8);
-  if (kv_timing)
     fprintf(stderr,
             "[kv_timing] validate: parse+p1 %.2f cache+enq %.2f (p2 %.2f mu %.2f "
             "rb %.2f) gpu-wait %.2f interp %.2f resolve %.2f muhash-wait %.2f "
             "total %.2f ms\n",
-            vt_ms(vt0, vt1), vt_ms(vt1, vt2), vt_ms(vt1, vt1a), vt_ms(vt1a, vt1b),
-            vt_ms(vt1b, vt2), vt_ms(vt2, vt3), vt_ms(vt3, vt4), vt_ms(vt4, vt5),
-            vt_ms(vt5, vt_now()), vt_ms(vt0, vt_now()));
+            ms(c.t_start, c.t_p1), ms(c.t_p1, c.t_rb), ms(c.t_p1, c.t_enq),
+            ms(c.t_enq, c.t_mu), ms(c.t_mu, c.t_rb), ms(c.t_rb, c.t_gpu),
+            ms(c.t_gpu, c.t_interp), ms(c.t_interp, c.t_resolve),
+            ms(c.t_resolve, now()), ms(c.t_start, now()));
+  }
   return 0;
 }
 
@@ -1797,13 +1745,7 @@ extern "C" int kv_validate_block(kv_ctx *ctx, const uint8_t *blob, size_t blob_l
                                  uint64_t pov_daa_score, uint64_t block_daa_score,
                                  uint32_t flags, int32_t *tx_codes_out,
                                  uint64_t *fees_out, uint8_t *muhash_partial_out) {
-  if (!ctx) {
-    set_error("kv_validate_block: null ctx");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   return validate_block_impl(ctx, blob, blob_len, pov_daa_score, block_daa_score,
                              flags, tx_codes_out, fees_out, muhash_partial_out,
                              nullptr);
@@ -1817,33 +1759,26 @@ extern "C" int kv_validate_block(kv_ctx *ctx, const uint8_t *blob, size_t blob_l
  * spk_len u32 ‖ spk[36] inline. */
 
 extern "C" int kv_utxo_reset(kv_ctx *ctx, uint64_t capacity) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   uint64_t cap = 64;
   while (cap < capacity * 2) cap <<= 1; /* ≤50% load factor */
-  if (ctx->d_utxo) (void)hipFree(ctx->d_utxo);
-  if (hipMalloc(&ctx->d_utxo, cap * sizeof(kv::utxo_slot)) != hipSuccess) {
-    ctx->d_utxo = nullptr;
-    ctx->utxo_cap = 0;
-    set_error("kv_utxo_reset: hipMalloc failed");
-    return -2;
-  }
-  HIP_CHECK(hipMemsetAsync(ctx->d_utxo, 0, cap * sizeof(kv::utxo_slot), ctx->stream));
-  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  ctx->utxo_cap = 0;
+  if (ctx->d_utxo.alloc(cap * sizeof(kv::utxo_slot))) return -2;
   ctx->utxo_cap = cap;
+  HIP_CHECK(hipMemsetAsync(ctx->d_utxo.p, 0, cap * sizeof(kv::utxo_slot), ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
   ctx->arena_head = 0; /* the spk arena compacts on reset (allocation kept) */
   return 0;
 }
 
 static int utxo_stage(kv_ctx *ctx, const uint8_t *outpoints, const uint8_t *values,
                       size_t n) {
-  if (ensure_cap((void **)&ctx->d_op_in, &ctx->d_op_cap, n * 36)) return -2;
-  HIP_CHECK(hipMemcpyAsync(ctx->d_op_in, outpoints, n * 36, hipMemcpyHostToDevice,
+  if (ctx->d_op_in.ensure(n * 36)) return -2;
+  HIP_CHECK(hipMemcpyAsync(ctx->d_op_in.p, outpoints, n * 36, hipMemcpyHostToDevice,
                            ctx->stream));
   if (values) {
-    if (ensure_cap((void **)&ctx->d_val_in, &ctx->d_val_cap, n * 64)) return -2;
-    HIP_CHECK(hipMemcpyAsync(ctx->d_val_in, values, n * 64, hipMemcpyHostToDevice,
+    if (ctx->d_val_in.ensure(n * 64)) return -2;
+    HIP_CHECK(hipMemcpyAsync(ctx->d_val_in.p, values, n * 64, hipMemcpyHostToDevice,
                              ctx->stream));
   }
   return 0;
@@ -1851,22 +1786,19 @@ static int utxo_stage(kv_ctx *ctx, const uint8_t *outpoints, const uint8_t *valu
 
 static int utxo_upsert_nolock(kv_ctx *ctx, const uint8_t *outpoints,
                               const uint8_t *entries64, size_t n) {
-  if (!ctx->d_utxo) {
+  if (!ctx->d_utxo.p) {
     set_error("kv_utxo_upsert: call kv_utxo_reset first");
     return -1;
   }
   int rc = utxo_stage(ctx, outpoints, entries64, n);
   if (rc) return rc;
-  int *d_fail = ctx->d_utxo_fail; /* per-ctx: a shared flag would race when
-                                     two contexts upsert concurrently */
-  if (!d_fail) {
-    HIP_CHECK(hipMalloc(&d_fail, 4));
-    ctx->d_utxo_fail = d_fail;
-  }
+  if (ctx->d_utxo_fail.ensure(4)) return -2;
+  int *d_fail = ctx->d_utxo_fail.as<int>();
   HIP_CHECK(hipMemsetAsync(d_fail, 0, 4, ctx->stream));
   hipLaunchKernelGGL(kv::kv_utxo_upsert_kernel, dim3(((uint32_t)n + 255) / 256),
-                     dim3(256), 0, ctx->stream, ctx->d_utxo, ctx->utxo_cap - 1,
-                     ctx->d_op_in, ctx->d_val_in, (unsigned long long)n, d_fail);
+                     dim3(256), 0, ctx->stream, ctx->table(), ctx->utxo_cap - 1,
+                     ctx->d_op_in.as<uint8_t>(), ctx->d_val_in.as<uint8_t>(),
+                     (unsigned long long)n, d_fail);
   int fail = 0;
   HIP_CHECK(hipMemcpyAsync(&fail, d_fail, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -1879,30 +1811,23 @@ static int utxo_upsert_nolock(kv_ctx *ctx, const uint8_t *outpoints,
 
 extern "C" int kv_utxo_upsert(kv_ctx *ctx, const uint8_t *outpoints,
                               const uint8_t *entries64, size_t n) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   return utxo_upsert_nolock(ctx, outpoints, entries64, n);
 }
 
 /* grow the spk arena to fit `need` more bytes; preserves contents */
 static int arena_reserve(kv_ctx *ctx, uint64_t need) {
   uint64_t want = ctx->arena_head + need;
-  if (want <= ctx->arena_cap) return 0;
-  uint64_t nc = ctx->arena_cap ? ctx->arena_cap : (1u << 20);
+  if (want <= ctx->d_arena.cap) return 0;
+  uint64_t nc = ctx->d_arena.cap ? ctx->d_arena.cap : (1u << 20);
   while (nc < want) nc *= 2;
-  uint8_t *na = nullptr;
-  if (hipMalloc(&na, nc) != hipSuccess) {
-    set_error("kv_utxo arena: hipMalloc failed");
-    return -2;
-  }
-  if (ctx->d_arena && ctx->arena_head)
-    HIP_CHECK(hipMemcpyAsync(na, ctx->d_arena, ctx->arena_head,
+  DeviceBuf na;
+  if (na.alloc(nc)) return -2;
+  if (ctx->arena_head)
+    HIP_CHECK(hipMemcpyAsync(na.p, ctx->d_arena.p, ctx->arena_head,
                              hipMemcpyDeviceToDevice, ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  if (ctx->d_arena) (void)hipFree(ctx->d_arena);
-  ctx->d_arena = na;
-  ctx->arena_cap = nc;
+  ctx->d_arena.swap(na); /* the old arena goes with `na` */
   return 0;
 }
 
@@ -1912,7 +1837,7 @@ static int arena_reserve(kv_ctx *ctx, uint64_t need) {
 static int utxo_upsert_spk_nolock(kv_ctx *ctx, const uint8_t *outpoints,
                                   const uint8_t *entries64, const uint8_t *spk_blob,
                                   size_t spk_blob_len, size_t n) {
-  if (!ctx->d_utxo) {
+  if (!ctx->d_utxo.p) {
     set_error("kv_utxo_upsert_spk: call kv_utxo_reset first");
     return -1;
   }
@@ -1937,7 +1862,7 @@ static int utxo_upsert_spk_nolock(kv_ctx *ctx, const uint8_t *outpoints,
   int rc = arena_reserve(ctx, long_total);
   if (rc) return rc;
   uint64_t base = ctx->arena_head;
-  HIP_CHECK(hipMemcpyAsync(ctx->d_arena + base, spk_blob, long_total,
+  HIP_CHECK(hipMemcpyAsync(ctx->d_arena.as<uint8_t>() + base, spk_blob, long_total,
                            hipMemcpyHostToDevice, ctx->stream));
   ctx->arena_head += long_total;
   /* rewrite the long entries: flags |= ARENA, spk[0..4) = arena offset */
@@ -1963,32 +1888,28 @@ static int utxo_upsert_spk_nolock(kv_ctx *ctx, const uint8_t *outpoints,
 extern "C" int kv_utxo_upsert_spk(kv_ctx *ctx, const uint8_t *outpoints,
                                   const uint8_t *entries64, const uint8_t *spk_blob,
                                   size_t spk_blob_len, size_t n) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   return utxo_upsert_spk_nolock(ctx, outpoints, entries64, spk_blob,
                                 spk_blob_len, n);
 }
 
 static int utxo_remove_nolock(kv_ctx *ctx, const uint8_t *outpoints, size_t n) {
-  if (!ctx->d_utxo) {
+  if (!ctx->d_utxo.p) {
     set_error("kv_utxo_remove: call kv_utxo_reset first");
     return -1;
   }
   int rc = utxo_stage(ctx, outpoints, nullptr, n);
   if (rc) return rc;
   hipLaunchKernelGGL(kv::kv_utxo_remove_kernel, dim3(((uint32_t)n + 255) / 256),
-                     dim3(256), 0, ctx->stream, ctx->d_utxo, ctx->utxo_cap - 1,
-                     ctx->d_op_in, (unsigned long long)n);
+                     dim3(256), 0, ctx->stream, ctx->table(), ctx->utxo_cap - 1,
+                     ctx->d_op_in.as<uint8_t>(), (unsigned long long)n);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return 0;
 }
 
 extern "C" int kv_utxo_remove(kv_ctx *ctx, const uint8_t *outpoints, size_t n) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   return utxo_remove_nolock(ctx, outpoints, n);
 }
 
@@ -2019,19 +1940,18 @@ static int arena_gather_nolock(kv_ctx *ctx, size_t n, TakeFn take,
   }
   out.resize(dst);
   if (jobs.empty()) return 0;
-  if (ensure_cap(&ctx->d_gjobs, &ctx->d_gjobs_cap,
-                 jobs.size() * sizeof(kv::arena_gather_job)) ||
-      ensure_cap(&ctx->d_gout, &ctx->d_gout_cap, dst))
+  if (ctx->d_gjobs.ensure(jobs.size() * sizeof(kv::arena_gather_job)) ||
+      ctx->d_gout.ensure(dst))
     return -2;
-  HIP_CHECK(hipMemcpyAsync(ctx->d_gjobs, jobs.data(),
+  HIP_CHECK(hipMemcpyAsync(ctx->d_gjobs.p, jobs.data(),
                            jobs.size() * sizeof(kv::arena_gather_job),
                            hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(kv::kv_arena_gather_kernel, dim3((uint32_t)jobs.size()),
-                     dim3(256), 0, ctx->stream, ctx->d_arena,
-                     (const kv::arena_gather_job *)ctx->d_gjobs,
-                     (uint32_t)jobs.size(), (uint8_t *)ctx->d_gout);
+                     dim3(256), 0, ctx->stream, ctx->d_arena.as<uint8_t>(),
+                     ctx->d_gjobs.as<const kv::arena_gather_job>(),
+                     (uint32_t)jobs.size(), ctx->d_gout.as<uint8_t>());
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpyAsync(out.data(), ctx->d_gout, dst, hipMemcpyDeviceToHost,
+  HIP_CHECK(hipMemcpyAsync(out.data(), ctx->d_gout.p, dst, hipMemcpyDeviceToHost,
                            ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return 0;
@@ -2041,9 +1961,7 @@ extern "C" int kv_utxo_lookup_spk(kv_ctx *ctx, const uint8_t *outpoints, size_t 
                                   uint8_t *entries_out, uint64_t *found_bitmap,
                                   uint8_t *spk_out, size_t spk_cap,
                                   size_t *spk_used) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   int rc = utxo_lookup_nolock(ctx, outpoints, n, entries_out, found_bitmap,
                               nullptr);
   if (rc) return rc;
@@ -2069,7 +1987,7 @@ extern "C" int kv_utxo_lookup_spk(kv_ctx *ctx, const uint8_t *outpoints, size_t 
 static int utxo_lookup_nolock(kv_ctx *ctx, const uint8_t *outpoints, size_t n,
                               uint8_t *entries_out, uint64_t *found_bitmap,
                               double *kernel_ms) {
-  if (!ctx->d_utxo) {
+  if (!ctx->d_utxo.p) {
     set_error("kv_utxo_lookup: call kv_utxo_reset first");
     return -1;
   }
@@ -2080,22 +1998,22 @@ static int utxo_lookup_nolock(kv_ctx *ctx, const uint8_t *outpoints, size_t n,
   if (rc) return rc;
   auto t1_ = tn();
   size_t words = (n + 63) / 64;
-  if (ensure_cap((void **)&ctx->d_ent_out, &ctx->d_ent_cap, n * 64)) return -2;
-  if (ensure_cap((void **)&ctx->d_bitmap, &ctx->d_bitmap_cap, words * 8)) return -2;
+  if (ctx->d_ent_out.ensure(n * 64) || ctx->d_bitmap.ensure(words * 8)) return -2;
   hipEvent_t t0, t1;
   HIP_CHECK(hipEventCreate(&t0));
   HIP_CHECK(hipEventCreate(&t1));
   HIP_CHECK(hipEventRecord(t0, ctx->stream));
   hipLaunchKernelGGL(kv::kv_utxo_lookup_kernel, dim3(((uint32_t)n + 255) / 256),
-                     dim3(256), 0, ctx->stream, ctx->d_utxo, ctx->utxo_cap - 1,
-                     ctx->d_op_in, (unsigned long long)n, ctx->d_ent_out,
-                     (unsigned long long *)ctx->d_bitmap);
+                     dim3(256), 0, ctx->stream, ctx->table(), ctx->utxo_cap - 1,
+                     ctx->d_op_in.as<uint8_t>(), (unsigned long long)n,
+                     ctx->d_ent_out.as<uint8_t>(),
+                     ctx->d_bitmap.as<unsigned long long>());
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipEventRecord(t1, ctx->stream));
   if (entries_out)
-    HIP_CHECK(hipMemcpyAsync(entries_out, ctx->d_ent_out, n * 64,
+    HIP_CHECK(hipMemcpyAsync(entries_out, ctx->d_ent_out.p, n * 64,
                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(found_bitmap, ctx->d_bitmap, words * 8,
+  HIP_CHECK(hipMemcpyAsync(found_bitmap, ctx->d_bitmap.p, words * 8,
                            hipMemcpyDeviceToHost, ctx->stream));
   auto t2_ = tn();
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -2117,9 +2035,7 @@ static int utxo_lookup_nolock(kv_ctx *ctx, const uint8_t *outpoints, size_t n,
 extern "C" int kv_utxo_lookup(kv_ctx *ctx, const uint8_t *outpoints, size_t n,
                               uint8_t *entries_out, uint64_t *found_bitmap,
                               double *kernel_ms) {
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   return utxo_lookup_nolock(ctx, outpoints, n, entries_out, found_bitmap,
                             kernel_ms);
 }
@@ -2148,23 +2064,18 @@ extern "C" int kv_utxo_commitment_window(void) { return (int)KV_COMMIT_WINDOW; }
 /* scratch for n_elems (<= KV_COMMIT_WINDOW) elements; the fixed part is one
  * allocation whose size depends on the compiled window alone */
 static int commit_scratch(kv_ctx *ctx, size_t n_elems) {
-  if (!ctx->d_cm_fixed &&
-      hipMalloc(&ctx->d_cm_fixed, CM_FIXED_BYTES) != hipSuccess) {
-    ctx->d_cm_fixed = nullptr;
-    set_error("kv_utxo commitment: hipMalloc failed (scratch)");
-    return -2;
-  }
-  return ensure_cap((void **)&ctx->d_cm_elems, &ctx->d_cm_elems_cap,
-                    n_elems * KVU_LIMBS * 8);
+  if (!ctx->d_cm_fixed.p && ctx->d_cm_fixed.alloc(CM_FIXED_BYTES)) return -2;
+  return ctx->d_cm_elems.ensure(n_elems * KVU_LIMBS * 8);
 }
 
 /* zero the copy-back record and set `lanes` running accumulators to one */
 static int commit_begin(kv_ctx *ctx, uint32_t lanes) {
-  HIP_CHECK(hipMemsetAsync(ctx->d_cm_fixed + CM_OFF_OUT, 0, CM_OFF_COUNT,
+  HIP_CHECK(hipMemsetAsync(ctx->d_cm_fixed.as<uint8_t>() + CM_OFF_OUT, 0, CM_OFF_COUNT,
                            ctx->stream));
   hipLaunchKernelGGL(kv::kv_u3072_fill_one_kernel,
                      dim3((lanes * KVU_LIMBS + 255) / 256), dim3(256), 0,
-                     ctx->stream, (uint64_t *)(ctx->d_cm_fixed + CM_OFF_ACC), lanes);
+                     ctx->stream,
+                     (uint64_t *)(ctx->d_cm_fixed.as<uint8_t>() + CM_OFF_ACC), lanes);
   return 0;
 }
 
@@ -2172,9 +2083,9 @@ static int commit_begin(kv_ctx *ctx, uint32_t lanes) {
  * schedule of enqueue_muhash), move it into the copy-back record and queue the
  * ONE device->host copy of the chain. The caller synchronises. */
 static int commit_finish(kv_ctx *ctx, uint32_t lanes, kv::commit_out *h_out) {
-  uint64_t *cur = (uint64_t *)(ctx->d_cm_fixed + CM_OFF_ACC);
-  uint64_t *pa = (uint64_t *)(ctx->d_cm_fixed + CM_OFF_PA);
-  uint64_t *pb = (uint64_t *)(ctx->d_cm_fixed + CM_OFF_PB);
+  uint64_t *cur = (uint64_t *)(ctx->d_cm_fixed.as<uint8_t>() + CM_OFF_ACC);
+  uint64_t *pa = (uint64_t *)(ctx->d_cm_fixed.as<uint8_t>() + CM_OFF_PA);
+  uint64_t *pb = (uint64_t *)(ctx->d_cm_fixed.as<uint8_t>() + CM_OFF_PB);
   uint32_t n_cur = lanes;
   while (n_cur > 1) {
     uint32_t stride = n_cur > 64 ? (n_cur + 63) / 64 : 1;
@@ -2185,7 +2096,7 @@ static int commit_finish(kv_ctx *ctx, uint32_t lanes, kv::commit_out *h_out) {
     cur = pa;
     std::swap(pa, pb);
   }
-  kv::commit_out *d_out = (kv::commit_out *)(ctx->d_cm_fixed + CM_OFF_OUT);
+  kv::commit_out *d_out = (kv::commit_out *)(ctx->d_cm_fixed.as<uint8_t>() + CM_OFF_OUT);
   hipLaunchKernelGGL(kv::kv_u3072_commit_out_kernel, dim3(1), dim3(64), 0,
                      ctx->stream, cur, d_out);
   HIP_CHECK(hipGetLastError());
@@ -2200,21 +2111,19 @@ extern "C" int kv_utxo_commitment(kv_ctx *ctx, uint8_t partial768_out[768],
     set_error("kv_utxo_commitment: null argument");
     return -1;
   }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   kv::u3072 one;
   kv::u3072_one(one);
   memcpy(partial768_out + 384, one.l, 384); /* denominator is always one */
   if (n_live_out) *n_live_out = 0;
   if (kernel_ms) *kernel_ms = 0.0;
-  if (!ctx->d_utxo) { /* never reset: the empty set */
+  if (!ctx->d_utxo.p) { /* never reset: the empty set */
     memcpy(partial768_out, one.l, 384);
     return 0;
   }
   int rc = commit_scratch(ctx, KV_COMMIT_WINDOW);
   if (rc) return rc;
-  uint8_t *fx = ctx->d_cm_fixed;
+  uint8_t *fx = ctx->d_cm_fixed.as<uint8_t>();
   kv::commit_out *d_out = (kv::commit_out *)(fx + CM_OFF_OUT);
   uint32_t *d_count = (uint32_t *)(fx + CM_OFF_COUNT);
   uint32_t *d_idx = (uint32_t *)(fx + CM_OFF_IDX);
@@ -2230,14 +2139,14 @@ extern "C" int kv_utxo_commitment(kv_ctx *ctx, uint8_t partial768_out[768],
     dim3 grid((n_slots + 255) / 256);
     if (hipMemsetAsync(d_count, 0, 16, ctx->stream) != hipSuccess) rc = -2;
     hipLaunchKernelGGL(kv::kv_utxo_commit_compact_kernel, grid, dim3(256), 0,
-                       ctx->stream, ctx->d_utxo, base, n_slots, d_idx, d_count);
+                       ctx->stream, ctx->table(), base, n_slots, d_idx, d_count);
     hipLaunchKernelGGL(kv::kv_utxo_commit_element_kernel, grid, dim3(256), 0,
-                       ctx->stream, ctx->d_utxo, base, (const uint32_t *)d_idx,
-                       (const uint32_t *)d_count, (const uint8_t *)ctx->d_arena,
-                       ctx->arena_head, ctx->d_cm_elems, d_out);
+                       ctx->stream, ctx->table(), base, (const uint32_t *)d_idx,
+                       (const uint32_t *)d_count, ctx->d_arena.as<const uint8_t>(),
+                       ctx->arena_head, ctx->d_cm_elems.as<uint64_t>(), d_out);
     hipLaunchKernelGGL(kv_u3072_reduce_wave_acc_kernel,
                        dim3(KV_COMMIT_LANES / 4), dim3(256), 0, ctx->stream,
-                       (const uint64_t *)ctx->d_cm_elems, (const uint32_t *)d_count,
+                       ctx->d_cm_elems.as<const uint64_t>(), (const uint32_t *)d_count,
                        0u, KV_COMMIT_LANES, d_acc, d_out);
   }
   kv::commit_out h_out;
@@ -2276,9 +2185,7 @@ extern "C" int kv_utxo_import_chunk(kv_ctx *ctx, const uint8_t *outpoints,
     set_error("kv_utxo_import_chunk: chunk too large");
     return -1;
   }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   int rc = utxo_upsert_spk_nolock(ctx, outpoints, entries64, spk_blob,
                                   spk_blob_len, n);
   if (rc) return rc;
@@ -2287,7 +2194,7 @@ extern "C" int kv_utxo_import_chunk(kv_ctx *ctx, const uint8_t *outpoints,
   size_t batch = std::min<size_t>(n, KV_COMMIT_WINDOW);
   rc = commit_scratch(ctx, batch);
   if (rc) return rc;
-  uint8_t *fx = ctx->d_cm_fixed;
+  uint8_t *fx = ctx->d_cm_fixed.as<uint8_t>();
   kv::commit_out *d_out = (kv::commit_out *)(fx + CM_OFF_OUT);
   uint64_t *d_acc = (uint64_t *)(fx + CM_OFF_ACC);
   /* about 8 elements per first-pass wave, at most KV_COMMIT_LANES waves */
@@ -2298,12 +2205,12 @@ extern "C" int kv_utxo_import_chunk(kv_ctx *ctx, const uint8_t *outpoints,
     uint32_t m = (uint32_t)std::min(batch, n - off);
     hipLaunchKernelGGL(kv::kv_utxo_chunk_element_kernel, dim3((m + 255) / 256),
                        dim3(256), 0, ctx->stream,
-                       (const uint8_t *)ctx->d_op_in + off * 36,
-                       (const uint8_t *)ctx->d_val_in + off * 64, m,
-                       (const uint8_t *)ctx->d_arena, ctx->arena_head,
-                       ctx->d_cm_elems, d_out);
+                       ctx->d_op_in.as<const uint8_t>() + off * 36,
+                       ctx->d_val_in.as<const uint8_t>() + off * 64, m,
+                       ctx->d_arena.as<const uint8_t>(), ctx->arena_head,
+                       ctx->d_cm_elems.as<uint64_t>(), d_out);
     hipLaunchKernelGGL(kv_u3072_reduce_wave_acc_kernel, dim3((lanes + 3) / 4),
-                       dim3(256), 0, ctx->stream, (const uint64_t *)ctx->d_cm_elems,
+                       dim3(256), 0, ctx->stream, ctx->d_cm_elems.as<const uint64_t>(),
                        (const uint32_t *)nullptr, m, lanes, d_acc, d_out);
   }
   kv::commit_out h_out;
@@ -2338,14 +2245,9 @@ static_assert(sizeof(kv::table_scan_rec) <= TR_OFF_REHASH &&
 /* the stats pass on ctx->stream: one kernel, one 40 B record back, one
  * synchronisation. Needs a table. */
 static int utxo_scan_nolock(kv_ctx *ctx, kv::table_scan_rec *h_rec, float *ms) {
-  if (!ctx->d_tbl_rec) {
-    if (hipMalloc(&ctx->d_tbl_rec, TR_BYTES) != hipSuccess) {
-      ctx->d_tbl_rec = nullptr;
-      set_error("kv_utxo table records: hipMalloc failed");
-      return -2;
-    }
-  }
-  kv::table_scan_rec *d_rec = (kv::table_scan_rec *)(ctx->d_tbl_rec + TR_OFF_SCAN);
+  if (ctx->d_tbl_rec.ensure(TR_BYTES)) return -2;
+  kv::table_scan_rec *d_rec =
+      (kv::table_scan_rec *)(ctx->d_tbl_rec.as<uint8_t>() + TR_OFF_SCAN);
   uint32_t blocks = (uint32_t)std::min<uint64_t>((ctx->utxo_cap + 255) / 256,
                                                  KV_STATS_MAX_BLOCKS);
   hipEvent_t t0, t1;
@@ -2360,7 +2262,7 @@ static int utxo_scan_nolock(kv_ctx *ctx, kv::table_scan_rec *h_rec, float *ms) {
     e = hipMemsetAsync(d_rec, 0, sizeof(kv::table_scan_rec), ctx->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(kv::kv_utxo_stats_kernel, dim3(blocks), dim3(256), 0,
-                       ctx->stream, (const kv::utxo_slot *)ctx->d_utxo,
+                       ctx->stream, ctx->table(),
                        ctx->utxo_cap, d_rec);
     e = hipGetLastError();
   }
@@ -2385,11 +2287,9 @@ extern "C" int kv_utxo_stats(kv_ctx *ctx, kv_utxo_table_stats *out) {
     set_error("kv_utxo_stats: null argument");
     return -1;
   }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   memset(out, 0, sizeof(*out));
-  if (!ctx->d_utxo) return 0; /* never reset */
+  if (!ctx->d_utxo.p) return 0; /* never reset */
   kv::table_scan_rec rec;
   int rc = utxo_scan_nolock(ctx, &rec, nullptr);
   if (rc) return rc;
@@ -2399,20 +2299,14 @@ extern "C" int kv_utxo_stats(kv_ctx *ctx, kv_utxo_table_stats *out) {
   out->n_empty = rec.n_empty;
   out->arena_used = ctx->arena_head;
   out->arena_live_bytes = rec.arena_live_bytes;
-  out->arena_cap = ctx->arena_cap;
+  out->arena_cap = ctx->d_arena.cap;
   return 0;
 }
 
 extern "C" int kv_utxo_rehash(kv_ctx *ctx, uint64_t capacity, double *kernel_ms) {
-  if (!ctx) {
-    set_error("kv_utxo_rehash: null ctx");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   if (kernel_ms) *kernel_ms = 0.0;
-  if (!ctx->d_utxo) {
+  if (!ctx->d_utxo.p) {
     set_error("kv_utxo_rehash: call kv_utxo_reset first");
     return -1;
   }
@@ -2440,49 +2334,33 @@ extern "C" int kv_utxo_rehash(kv_ctx *ctx, uint64_t capacity, double *kernel_ms)
   /* the fresh arena: arena_reserve's rounding (1 MiB doubled until it fits);
    * a context that already owns an arena keeps at least that minimum */
   uint64_t new_arena_cap = 0;
-  if (ctx->d_arena || scan.arena_live_bytes) {
+  if (ctx->d_arena.p || scan.arena_live_bytes) {
     new_arena_cap = 1u << 20;
     while (new_arena_cap < scan.arena_live_bytes) new_arena_cap *= 2;
   }
   const uint32_t jobs_cap = (uint32_t)scan.n_arena;
   rc = commit_scratch(ctx, 0); /* index list and count word */
   if (rc) return rc;
-  if (jobs_cap && ensure_cap(&ctx->d_gjobs, &ctx->d_gjobs_cap,
-                             (size_t)jobs_cap * sizeof(kv::arena_gather_job)))
+  if (ctx->d_gjobs.ensure((size_t)jobs_cap * sizeof(kv::arena_gather_job)))
     return -2;
 
-  kv::utxo_slot *nt = nullptr;
-  uint8_t *na = nullptr;
+  /* the new table and arena live in locals until the chain has run clean:
+   * every failure below leaves the old table in place and frees these */
+  DeviceBuf nt, na;
+  if (nt.alloc(new_cap * sizeof(kv::utxo_slot))) return -2;
+  if (new_arena_cap && na.alloc(new_arena_cap)) return -2;
   hipEvent_t t0 = nullptr, t1 = nullptr;
-  auto discard = [&]() { /* every failure below leaves the old table in place */
-    if (nt) (void)hipFree(nt);
-    if (na) (void)hipFree(na);
-    if (t0) (void)hipEventDestroy(t0);
-    if (t1) (void)hipEventDestroy(t1);
-  };
-  if (hipMalloc(&nt, new_cap * sizeof(kv::utxo_slot)) != hipSuccess) {
-    nt = nullptr;
-    (void)hipGetLastError();
-    set_error("kv_utxo_rehash: hipMalloc failed (table)");
-    return -2;
-  }
-  if (new_arena_cap && hipMalloc(&na, new_arena_cap) != hipSuccess) {
-    na = nullptr;
-    (void)hipGetLastError();
-    discard();
-    set_error("kv_utxo_rehash: hipMalloc failed (arena)");
-    return -2;
-  }
-  uint8_t *fx = ctx->d_cm_fixed;
+  uint8_t *fx = ctx->d_cm_fixed.as<uint8_t>();
   uint32_t *d_count = (uint32_t *)(fx + CM_OFF_COUNT);
   uint32_t *d_idx = (uint32_t *)(fx + CM_OFF_IDX);
-  kv::rehash_rec *d_rec = (kv::rehash_rec *)(ctx->d_tbl_rec + TR_OFF_REHASH);
+  kv::rehash_rec *d_rec =
+      (kv::rehash_rec *)(ctx->d_tbl_rec.as<uint8_t>() + TR_OFF_REHASH);
   kv::rehash_rec h_rec;
   hipError_t e = hipEventCreate(&t0);
   if (e == hipSuccess) e = hipEventCreate(&t1);
   if (e == hipSuccess) e = hipEventRecord(t0, ctx->stream);
   if (e == hipSuccess)
-    e = hipMemsetAsync(nt, 0, new_cap * sizeof(kv::utxo_slot), ctx->stream);
+    e = hipMemsetAsync(nt.p, 0, new_cap * sizeof(kv::utxo_slot), ctx->stream);
   if (e == hipSuccess)
     e = hipMemsetAsync(d_rec, 0, sizeof(kv::rehash_rec), ctx->stream);
   for (uint64_t base = 0; e == hipSuccess && base < ctx->utxo_cap;
@@ -2493,19 +2371,21 @@ extern "C" int kv_utxo_rehash(kv_ctx *ctx, uint64_t capacity, double *kernel_ms)
     e = hipMemsetAsync(d_count, 0, 16, ctx->stream);
     if (e != hipSuccess) break;
     hipLaunchKernelGGL(kv::kv_utxo_commit_compact_kernel, grid, dim3(256), 0,
-                       ctx->stream, ctx->d_utxo, base, n_slots, d_idx, d_count);
+                       ctx->stream, ctx->table(), base, n_slots, d_idx, d_count);
     hipLaunchKernelGGL(kv::kv_utxo_rehash_insert_kernel, grid, dim3(256), 0,
-                       ctx->stream, (const kv::utxo_slot *)ctx->d_utxo, base,
-                       (const uint32_t *)d_idx, (const uint32_t *)d_count, nt,
-                       new_cap - 1, ctx->arena_head, new_arena_cap,
-                       (kv::arena_gather_job *)ctx->d_gjobs, jobs_cap, d_rec);
+                       ctx->stream, ctx->table(), base,
+                       (const uint32_t *)d_idx, (const uint32_t *)d_count,
+                       nt.as<kv::utxo_slot>(), new_cap - 1, ctx->arena_head,
+                       new_arena_cap,
+                       ctx->d_gjobs.as<kv::arena_gather_job>(), jobs_cap, d_rec);
     e = hipGetLastError();
   }
   if (e == hipSuccess && jobs_cap) {
     hipLaunchKernelGGL(kv::kv_arena_copy_jobs_kernel, dim3(jobs_cap), dim3(256), 0,
-                       ctx->stream, (const uint8_t *)ctx->d_arena,
-                       (const kv::arena_gather_job *)ctx->d_gjobs,
-                       (const uint32_t *)&d_rec->n_jobs, jobs_cap, na);
+                       ctx->stream, ctx->d_arena.as<const uint8_t>(),
+                       ctx->d_gjobs.as<const kv::arena_gather_job>(),
+                       (const uint32_t *)&d_rec->n_jobs, jobs_cap,
+                       na.as<uint8_t>());
     e = hipGetLastError();
   }
   if (e == hipSuccess)
@@ -2516,33 +2396,24 @@ extern "C" int kv_utxo_rehash(kv_ctx *ctx, uint64_t capacity, double *kernel_ms)
   hipError_t e2 = hipStreamSynchronize(ctx->stream);
   float ms = 0.f;
   if (e == hipSuccess && e2 == hipSuccess) (void)hipEventElapsedTime(&ms, t0, t1);
-  if (e != hipSuccess || e2 != hipSuccess) {
-    discard();
-    HIP_CHECK(e);
-    HIP_CHECK(e2);
-  }
+  if (t0) (void)hipEventDestroy(t0);
+  if (t1) (void)hipEventDestroy(t1);
+  HIP_CHECK(e);
+  HIP_CHECK(e2);
   if (h_rec.fail || h_rec.inserted != scan.n_live ||
       h_rec.arena_head != scan.arena_live_bytes) {
-    discard();
     set_error(h_rec.fail
                   ? "kv_utxo_rehash: an entry could not be placed (script reference "
                     "out of range, or no room)"
                   : "kv_utxo_rehash: inserted count differs from the live count");
     return -3;
   }
-  /* device work complete and clean: swap, then free the old allocations */
-  kv::utxo_slot *old_t = ctx->d_utxo;
-  uint8_t *old_a = ctx->d_arena;
-  ctx->d_utxo = nt;
+  /* device work complete and clean: swap; the old allocations go with the
+   * locals */
+  ctx->d_utxo.swap(nt);
   ctx->utxo_cap = new_cap;
-  ctx->d_arena = na;
-  ctx->arena_cap = new_arena_cap;
+  ctx->d_arena.swap(na);
   ctx->arena_head = h_rec.arena_head;
-  nt = nullptr;
-  na = nullptr;
-  discard(); /* the events */
-  (void)hipFree(old_t);
-  if (old_a) (void)hipFree(old_a);
   if (kernel_ms) *kernel_ms = (double)scan_ms + (double)ms;
   return 0;
 }
@@ -2561,9 +2432,7 @@ extern "C" int kv_utxo_export_chunk(kv_ctx *ctx, uint64_t *cursor, size_t max_en
     set_error("kv_utxo_export_chunk: spk_cap below KV_UTXO_MAX_SPK");
     return -1;
   }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   if (*cursor >= ctx->utxo_cap) { /* the walk is over (or there is no table) */
     *cursor = ctx->utxo_cap;
     return 0;
@@ -2584,21 +2453,23 @@ extern "C" int kv_utxo_export_chunk(kv_ctx *ctx, uint64_t *cursor, size_t max_en
       std::min<uint64_t>(want, to_boundary), ctx->utxo_cap - base);
   int rc = commit_scratch(ctx, 0);
   if (rc) return rc;
-  if (ensure_cap((void **)&ctx->d_op_in, &ctx->d_op_cap, (size_t)span * 36) ||
-      ensure_cap((void **)&ctx->d_ent_out, &ctx->d_ent_cap, (size_t)span * 64) ||
-      ensure_cap((void **)&ctx->d_exp_refs, &ctx->d_exp_refs_cap, (size_t)span * 8))
+  if (ctx->d_op_in.ensure((size_t)span * 36) ||
+      ctx->d_ent_out.ensure((size_t)span * 64) ||
+      ctx->d_exp_refs.ensure((size_t)span * 8))
     return -2;
-  uint8_t *fx = ctx->d_cm_fixed;
+  uint8_t *fx = ctx->d_cm_fixed.as<uint8_t>();
   uint32_t *d_count = (uint32_t *)(fx + CM_OFF_COUNT);
   uint32_t *d_idx = (uint32_t *)(fx + CM_OFF_IDX);
   dim3 grid((span + 255) / 256);
   HIP_CHECK(hipMemsetAsync(d_count, 0, 16, ctx->stream));
   hipLaunchKernelGGL(kv::kv_utxo_commit_compact_kernel, grid, dim3(256), 0,
-                     ctx->stream, ctx->d_utxo, base, span, d_idx, d_count);
+                     ctx->stream, ctx->table(), base, span, d_idx, d_count);
   hipLaunchKernelGGL(kv::kv_utxo_export_gather_kernel, grid, dim3(256), 0,
-                     ctx->stream, (const kv::utxo_slot *)ctx->d_utxo, base,
+                     ctx->stream, ctx->table(), base,
                      (const uint32_t *)d_idx, (const uint32_t *)d_count,
-                     ctx->arena_head, ctx->d_op_in, ctx->d_ent_out, ctx->d_exp_refs);
+                     ctx->arena_head, ctx->d_op_in.as<uint8_t>(),
+                     ctx->d_ent_out.as<uint8_t>(),
+                     ctx->d_exp_refs.as<unsigned long long>());
   HIP_CHECK(hipGetLastError());
   uint32_t count = 0;
   HIP_CHECK(hipMemcpyAsync(&count, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2618,11 +2489,11 @@ extern "C" int kv_utxo_export_chunk(kv_ctx *ctx, uint64_t *cursor, size_t max_en
   vals.resize((size_t)count * 64);
   HIP_CHECK(hipMemcpyAsync(idx.data(), d_idx, (size_t)count * 4,
                            hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(refs.data(), ctx->d_exp_refs, (size_t)count * 8,
+  HIP_CHECK(hipMemcpyAsync(refs.data(), ctx->d_exp_refs.p, (size_t)count * 8,
                            hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(keys.data(), ctx->d_op_in, (size_t)count * 36,
+  HIP_CHECK(hipMemcpyAsync(keys.data(), ctx->d_op_in.p, (size_t)count * 36,
                            hipMemcpyDeviceToHost, ctx->stream));
-  HIP_CHECK(hipMemcpyAsync(vals.data(), ctx->d_ent_out, (size_t)count * 64,
+  HIP_CHECK(hipMemcpyAsync(vals.data(), ctx->d_ent_out.p, (size_t)count * 64,
                            hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
   /* compaction order is whatever the waves' atomics made it: sort into slot
@@ -2650,19 +2521,18 @@ extern "C" int kv_utxo_export_chunk(kv_ctx *ctx, uint64_t *cursor, size_t max_en
     memcpy(entries_out + m * 64, vals.data() + (size_t)p * 64, 64);
   }
   if (!jobs.empty()) {
-    if (ensure_cap(&ctx->d_gjobs, &ctx->d_gjobs_cap,
-                   jobs.size() * sizeof(kv::arena_gather_job)) ||
-        ensure_cap(&ctx->d_gout, &ctx->d_gout_cap, used))
+    if (ctx->d_gjobs.ensure(jobs.size() * sizeof(kv::arena_gather_job)) ||
+        ctx->d_gout.ensure(used))
       return -2;
-    HIP_CHECK(hipMemcpyAsync(ctx->d_gjobs, jobs.data(),
+    HIP_CHECK(hipMemcpyAsync(ctx->d_gjobs.p, jobs.data(),
                              jobs.size() * sizeof(kv::arena_gather_job),
                              hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(kv::kv_arena_gather_kernel, dim3((uint32_t)jobs.size()),
-                       dim3(256), 0, ctx->stream, ctx->d_arena,
-                       (const kv::arena_gather_job *)ctx->d_gjobs,
-                       (uint32_t)jobs.size(), (uint8_t *)ctx->d_gout);
+                       dim3(256), 0, ctx->stream, ctx->d_arena.as<uint8_t>(),
+                       ctx->d_gjobs.as<const kv::arena_gather_job>(),
+                       (uint32_t)jobs.size(), ctx->d_gout.as<uint8_t>());
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(spk_out, ctx->d_gout, used, hipMemcpyDeviceToHost,
+    HIP_CHECK(hipMemcpyAsync(spk_out, ctx->d_gout.p, used, hipMemcpyDeviceToHost,
                              ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
   }
@@ -2693,13 +2563,7 @@ extern "C" int kv_validate_mempool(kv_ctx *ctx, const uint8_t *blob,
                                    size_t blob_len, uint64_t pov_daa_score,
                                    double feerate_threshold, int from_utxo_table,
                                    int32_t *tx_codes_out, uint64_t *fees_out) {
-  if (!ctx) {
-    set_error("kv_validate_mempool: null ctx");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   vector<HTx> txs;
   int n_txs = parse_blob_host(blob, blob_len, txs);
   if (n_txs < 0) {
@@ -2712,7 +2576,7 @@ extern "C" int kv_validate_mempool(kv_ctx *ctx, const uint8_t *blob,
   vector<HTx> ptxs;
   const vector<HTx> *use_txs = &txs;
   if (from_utxo_table) {
-    if (!ctx->d_utxo) {
+    if (!ctx->d_utxo.p) {
       set_error("kv_validate_mempool: call kv_utxo_reset first");
       return -1;
     }
@@ -2762,14 +2626,8 @@ extern "C" int kv_validate_mempool(kv_ctx *ctx, const uint8_t *blob,
 extern "C" int kv_block_body_check(kv_ctx *ctx, const uint8_t *blob,
                                    size_t blob_len, uint8_t merkle_root_out[32],
                                    int32_t *rule_code_out) {
-  if (!ctx) {
-    set_error("kv_block_body_check: null ctx");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
-  ValidateBufs &vb = vb_of(ctx);
+  KV_ENTER(ctx);
+  ValidateBufs &vb = ctx->vb;
   vector<HTx> txs;
   int n_txs = parse_blob_host(blob, blob_len, txs);
   if (n_txs < 0) {
@@ -3045,14 +2903,8 @@ extern "C" int kv_validate_block_utxo(kv_ctx *ctx, const uint8_t *blob,
                                       int apply_diff, int32_t *tx_codes_out,
                                       uint64_t *fees_out,
                                       uint8_t *muhash_partial_out) {
-  if (!ctx) {
-    set_error("kv_validate_block_utxo: null ctx");
-    return -1;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
-  if (!ctx->d_utxo) {
+  KV_ENTER(ctx);
+  if (!ctx->d_utxo.p) {
     set_error("kv_validate_block_utxo: call kv_utxo_reset first");
     return -1;
   }
@@ -3172,55 +3024,38 @@ extern "C" int kv_test_u3072_reduce(kv_ctx *ctx, const uint64_t *elements, uint3
     set_error("kv_test_u3072_reduce: bad argument");
     return -1;
   }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  (void)hipGetLastError(); /* clear any stale per-thread error so the
-      launch-config checks below only see THIS call's launches */
+  KV_ENTER(ctx);
   const size_t elem_bytes = KVU_LIMBS * sizeof(uint64_t);
   DeviceBuf d_elems, d_res, d_rec;
-  int rc = 0;
   kv::commit_out h_rec;
-  hipError_t e = hipSuccess;
   if (d_elems.ensure((n ? n : 1) * elem_bytes) || d_res.ensure(stride * elem_bytes) ||
-      d_rec.ensure(sizeof(kv::commit_out))) {
-    rc = -2;
-    goto done;
-  }
-#define KV_TRY(expr)                                                           \
-  if ((e = (expr)) != hipSuccess) {                                            \
-    set_error_loc(hipGetErrorString(e), __FILE__, __LINE__, #expr);            \
-    rc = -2;                                                                   \
-    goto done;                                                                 \
-  }
+      d_rec.ensure(sizeof(kv::commit_out)))
+    return -2;
   if (n)
-    KV_TRY(hipMemcpyAsync(d_elems.p, elements, n * elem_bytes, hipMemcpyHostToDevice,
-                          ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(d_elems.p, elements, n * elem_bytes,
+                             hipMemcpyHostToDevice, ctx->stream));
   if (acc_in) {
-    KV_TRY(hipMemcpyAsync(d_res.p, acc_in, stride * elem_bytes, hipMemcpyHostToDevice,
-                          ctx->stream));
-    KV_TRY(hipMemsetAsync(d_rec.p, 0, sizeof(kv::commit_out), ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(d_res.p, acc_in, stride * elem_bytes,
+                             hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemsetAsync(d_rec.p, 0, sizeof(kv::commit_out), ctx->stream));
     hipLaunchKernelGGL(kv_u3072_reduce_wave_acc_kernel, dim3((stride + 3) / 4),
-                       dim3(256), 0, ctx->stream, (const uint64_t *)d_elems.p,
-                       (const uint32_t *)nullptr, n, stride, (uint64_t *)d_res.p,
-                       (kv::commit_out *)d_rec.p);
+                       dim3(256), 0, ctx->stream, d_elems.as<const uint64_t>(),
+                       (const uint32_t *)nullptr, n, stride, d_res.as<uint64_t>(),
+                       d_rec.as<kv::commit_out>());
   } else {
     hipLaunchKernelGGL(kv_u3072_reduce_wave_kernel, dim3((stride + 3) / 4), dim3(256),
-                       0, ctx->stream, (const uint64_t *)d_elems.p, n, stride,
-                       (uint64_t *)d_res.p);
+                       0, ctx->stream, d_elems.as<const uint64_t>(), n, stride,
+                       d_res.as<uint64_t>());
   }
-  KV_TRY(hipGetLastError());
-  KV_TRY(hipStreamSynchronize(ctx->stream));
-  KV_TRY(hipMemcpy(out, d_res.p, stride * elem_bytes, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  HIP_CHECK(hipMemcpy(out, d_res.p, stride * elem_bytes, hipMemcpyDeviceToHost));
   if (n_live_out) {
     *n_live_out = 0;
     if (acc_in) {
-      KV_TRY(hipMemcpy(&h_rec, d_rec.p, sizeof(h_rec), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(&h_rec, d_rec.p, sizeof(h_rec), hipMemcpyDeviceToHost));
       *n_live_out = h_rec.n_live;
     }
   }
-#undef KV_TRY
-done:
-  if (d_elems.p) (void)hipFree(d_elems.p);
-  if (d_res.p) (void)hipFree(d_res.p);
-  if (d_rec.p) (void)hipFree(d_rec.p);
-  return rc;
+  return 0;
 }

@@ -58,6 +58,57 @@ def test_validate_block_parity(oracle, engine, kwargs, flags):
     assert emh == omh
 
 
+class KvTimings(ctypes.Structure):
+    _fields_ = [("subhash_ms", ctypes.c_double),
+                ("s_assemble_ms", ctypes.c_double),
+                ("e_assemble_ms", ctypes.c_double),
+                ("schnorr_ms", ctypes.c_double),
+                ("ecdsa_ms", ctypes.c_double),
+                ("muhash_ms", ctypes.c_double),
+                ("n_schnorr", ctypes.c_uint64),
+                ("n_ecdsa", ctypes.c_uint64)]
+
+
+# (seed, n_txs, pct_ecdsa): small, large, small again. The seeds are picked so
+# that every block holds ECDSA and Schnorr inputs, and the 300-tx block holds
+# accepted txs and corrupted signatures (asserted below on the oracle's output).
+GROW_THEN_REUSE_BLOCKS = [(31, 4, 50), (32, 300, 10), (33, 4, 50)]
+
+
+def test_validate_buffers_grow_then_reuse(oracle):
+    """Three blocks of 4, 300 and 4 txs through ONE fresh context, FULL flags
+    with muhash: both verify lanes' device and pinned buffers are allocated at
+    a small size, grown by the large block and reused by a small one, and the
+    large block's rejected signatures force the muhash re-enqueue over the
+    exact accept set. Codes, fees and the finalised muhash match the oracle
+    for every block."""
+    from rusty_kaspa_amd.engine import Engine
+    FULL = 0
+    eng = Engine()
+    try:
+        for seed, n, pct_ecdsa in GROW_THEN_REUSE_BLOCKS:
+            blob, meta = gen_block(oracle, seed=seed, n_txs=n, pct_multi_input=20,
+                                   pct_ecdsa=pct_ecdsa, pct_multisig=10,
+                                   pct_invalid=15)
+            oc, of, omh = oracle_validate(oracle, blob, n, FULL)
+            if n == 300:
+                assert 0 in oc
+                # 100 + script error: the input's signature script failed
+                assert any(100 < c < 200 for c in oc)
+            ec, ef, emh = engine_validate(eng, blob, n, FULL)
+            assert ec == oc, [(i, a, b) for i, (a, b) in enumerate(zip(ec, oc))
+                              if a != b][:5]
+            assert ef == of
+            assert emh == omh
+            tm = KvTimings()
+            assert eng.lib.kv_get_validate_timings(ctypes.c_void_p(eng.ctx),
+                                                   ctypes.byref(tm)) == 0
+            assert tm.n_schnorr > 0 and tm.n_ecdsa > 0, (seed, tm.n_schnorr,
+                                                         tm.n_ecdsa)
+    finally:
+        eng.close()
+
+
 def test_sighash_batch_parity(oracle, engine):
     import random
     rng = random.Random(5)
