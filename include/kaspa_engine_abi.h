@@ -30,6 +30,15 @@
  *   kv_utxo_commitment_window  slots per scan window of kv_utxo_commitment
  *   kv_utxo_import_chunk    ⇔ Consensus::append_imported_pruning_point_utxos
  *                             (consensus/src/consensus/mod.rs:1139-1152)
+ *   kv_utxo_apply_diff      ⇔ write_diff_batch (consensus/src/model/stores/
+ *                             utxo_set.rs:107-112), keeping the diff's inverse
+ *   kv_utxo_revert          ⇔ with_diff_in_place(as_reversed) of one chain
+ *                             block (processor.rs:410, utxo_diff.rs:71)
+ *   kv_utxo_journal_drop    ⇔ the stored diffs of blocks past finality depth
+ *                             going away
+ *   kv_utxo_journal_stats   what the undo journal holds
+ *   kv_validate_block_utxo_undo  kv_validate_block_utxo(apply_diff = 1) with a
+ *                             revertible diff
  *
  * No torch types cross this boundary: plain pointers and sizes only.
  * See INTEGRATION.md for the Rust-side binding a maintainer would add.
@@ -415,6 +424,86 @@ int kv_utxo_export_chunk(kv_ctx *ctx, uint64_t *cursor /* in/out, slot index; st
                          uint8_t *spk_out, size_t spk_cap, size_t *spk_used,
                          size_t *n_out);
 
+/* ---- undo journal: a reorg reverts diffs on the device ----
+ * ⇔ calculate_utxo_state_relatively (consensus/src/pipeline/virtual_processor/
+ *   processor.rs:393-437): down the old chain each block's stored diff is
+ *   applied reversed (with_diff_in_place(&mergeset_diff.as_reversed()), :410;
+ *   UtxoDiff::as_reversed, consensus/core/src/utxo/utxo_diff.rs:71), up the
+ *   new chain diffs are committed with write_diff_batch
+ *   (consensus/src/model/stores/utxo_set.rs:107-112).
+ * The reference keeps every chain block's diff in a store; here each journaled
+ * apply pushes one undo record onto a per-context journal in device memory.
+ * A record holds the diff's outpoints, the 64-byte value each one had (and
+ * whether it had one) before the diff, and its own copy of the long scripts
+ * among them: about 100 B per outpoint plus those scripts. It holds no slot
+ * index and no offset into the live arena, so kv_utxo_rehash leaves the
+ * journal valid. kv_utxo_reset clears the journal, kv_destroy frees it.
+ * Tokens are per context, start at 1 and only grow (also across resets). */
+typedef struct kv_utxo_diff_result {
+  uint64_t n_removed_missing; /* removed outpoints that were not in the set */
+  uint64_t n_added_overwrote; /* added outpoints that were already in the set */
+  uint64_t journal_bytes;     /* device bytes of the record this call pushed */
+  double kernel_ms;           /* capture + script copy + upsert kernels */
+} kv_utxo_diff_result;
+
+/* ⇔ write_diff_batch (utxo_set.rs:107-112: delete the removed keys, write the
+ *   added ones), with the inverse kept.
+ * removed_ops has the input format of kv_utxo_remove (n_removed × 36 B); the
+ * added side that of kv_utxo_upsert_spk. The table effect is exactly "remove,
+ * then upsert_spk". One record is pushed even when both sides are empty, so
+ * one block is always one token (*undo_token_out, required).
+ * The reference unwrap()s on a removed key that is missing and on an added key
+ * that exists; the engine applies and journals both faithfully and counts them
+ * in res_out, so a host can treat a non-zero count as a consistency alarm.
+ * Outpoints must be distinct across removed ∪ added: otherwise -1, nothing
+ * changed. Device chain on the context's stream: one launch probes every
+ * outpoint once, copies what it finds into the record and tombstones the
+ * removed side; one synchronisation brings back a 32 B record (counts, script
+ * bytes); a block-per-script copy fills the record's script blob; then the
+ * upsert of kv_utxo_upsert_spk runs.
+ * Failure atomicity: if the call fails after it began to mutate (-3: table
+ * full, or a stored script reference out of range), the engine reverts what
+ * it did from the record it just captured, drops that record and returns the
+ * error with the set unchanged (arena bytes spent on the attempt stay spent
+ * until the next kv_utxo_rehash). Should that internal revert itself fail (-2,
+ * out of device memory), the record stays the newest one. */
+int kv_utxo_apply_diff(kv_ctx *ctx, const uint8_t *removed_ops, size_t n_removed,
+                       const uint8_t *added_ops, const uint8_t *added_entries64,
+                       const uint8_t *spk_blob, size_t spk_blob_len, size_t n_added,
+                       kv_utxo_diff_result *res_out /*optional*/,
+                       uint64_t *undo_token_out);
+
+/* ⇔ with_diff_in_place(as_reversed) of one chain block (processor.rs:410).
+ * Applies the exact inverse of the record `token` names and pops it: added
+ * outpoints that were absent before are removed; added outpoints that
+ * overwrote an entry get the old entry back; removed outpoints that were
+ * present are re-inserted with their original 64 bytes (and script, for arena
+ * entries: the record's scripts are appended to the arena); removed outpoints
+ * that were missing are left alone.
+ * Strictly last-in-first-out: a token that is not the newest unreverted
+ * record returns -1 and changes nothing.
+ * Contract: the revert is exact if the set is in the state the matching apply
+ * left it in. Non-journaled mutations in between (kv_utxo_upsert[_spk],
+ * kv_utxo_remove, kv_utxo_import_chunk, kv_validate_block_utxo with
+ * apply_diff) are the caller's business; kv_utxo_rehash is not a mutation.
+ * Returns -3, with the record kept, if the table is too full to take the
+ * entries back. */
+int kv_utxo_revert(kv_ctx *ctx, uint64_t token);
+
+/* Frees every record with token <= upto_token: blocks past finality depth,
+ * which no reorg can reach. Returns 0 also when there is none. */
+int kv_utxo_journal_drop(kv_ctx *ctx, uint64_t upto_token);
+
+typedef struct kv_utxo_journal_info {
+  uint64_t n_records;
+  uint64_t oldest_token; /* 0 when the journal is empty */
+  uint64_t newest_token; /* 0 when the journal is empty */
+  uint64_t device_bytes; /* device memory the records hold */
+  double last_revert_kernel_ms; /* of the last kv_utxo_revert: the blob append
+                                   and its two launches */
+} kv_utxo_journal_info;
+int kv_utxo_journal_stats(kv_ctx *ctx, kv_utxo_journal_info *out);
+
 /* Populate + validate + (optionally) apply the UTXO diff — the full virtual
  * processor step for one block (utxo_validation.rs:351-390 populate, then
  * validation, then utxo_diff.rs:224 add_transaction per accepted tx).
@@ -428,6 +517,22 @@ int kv_validate_block_utxo(kv_ctx *ctx, const uint8_t *blob, size_t blob_len,
                            uint64_t pov_daa_score, uint64_t block_daa_score,
                            uint32_t flags, int apply_diff, int32_t *tx_codes_out,
                            uint64_t *fees_out, uint8_t *muhash_partial_out);
+
+/* kv_validate_block_utxo with apply_diff = 1 whose diff can be reverted ⇔ the
+ * same virtual processor step, with the block's diff kept as the reference
+ * keeps it for calculate_utxo_state_relatively (processor.rs:393-437).
+ * Codes, fees and the muhash partial are those of apply_diff = 1; the accepted
+ * txs' diff goes through kv_utxo_apply_diff's path and *undo_token_out
+ * (required) names its record for kv_utxo_revert. A block of which no tx is
+ * accepted still pushes an (empty) record. If two accepted txs spend one
+ * outpoint, or the diff fails to apply, the error of kv_utxo_apply_diff is
+ * returned with the set unchanged and no record pushed (the outputs are
+ * already filled in): run kv_block_body_check first. */
+int kv_validate_block_utxo_undo(kv_ctx *ctx, const uint8_t *blob, size_t blob_len,
+                                uint64_t pov_daa_score, uint64_t block_daa_score,
+                                uint32_t flags, int32_t *tx_codes_out,
+                                uint64_t *fees_out, uint8_t *muhash_partial_out,
+                                uint64_t *undo_token_out);
 
 /* Mempool batch validation ⇔ validate_mempool_transaction_in_utxo_context
  * (utxo_validation.rs:418-457) fanned over independent txs: SkipMassCheck +

@@ -20,6 +20,7 @@
 #include <string>
 #include <array>
 #include <chrono>
+#include <deque>
 #include <unordered_map>
 
 /* kernels compiled into this TU (single translation unit keeps the build to one
@@ -29,6 +30,7 @@
 #include "kv_utxo_kernels.hip"
 #include "kv_utxo_commit_kernels.hip"
 #include "kv_utxo_rehash_kernels.hip"
+#include "kv_utxo_journal_kernels.hip"
 #include "kv_validate_host.inc"
 #include "kv_script_host.inc"
 
@@ -148,6 +150,27 @@ struct ValidateBufs {
   VerifyLane lane[2] = {{{128, 96, 0, 2, 6}}, {{132, 97, 1, 4, 8}}};
 };
 
+/* One undo record of the journal (kv_utxo_apply_diff): rows are the diff's
+ * outpoints, removed side first. `fixed` is values (64 B a row) ‖ keys (36 B a
+ * row) ‖ found bitmap (a bit a row), `blob` the long scripts among the values,
+ * which refer to them by blob offset. Nothing here names a slot or a live
+ * arena offset, so a rehash leaves it valid. */
+struct JournalRecord {
+  uint64_t token = 0;
+  size_t n_removed = 0, n_added = 0;
+  DeviceBuf fixed, blob;
+  uint64_t blob_bytes = 0;
+  size_t n() const { return n_removed + n_added; }
+  size_t off_found() const { return (n() * (64 + 36) + 7) & ~(size_t)7; }
+  size_t fixed_bytes() const { return off_found() + (n() + 63) / 64 * 8; }
+  uint64_t device_bytes() const { return fixed.cap + blob.cap; }
+  uint8_t *vals() const { return fixed.as<uint8_t>(); }
+  uint8_t *keys() const { return fixed.as<uint8_t>() + n() * 64; }
+  unsigned long long *found() const {
+    return (unsigned long long *)(fixed.as<uint8_t>() + off_found());
+  }
+};
+
 struct kv_ctx {
   kv_params params;
   hipStream_t stream = nullptr;
@@ -207,6 +230,12 @@ struct kv_ctx {
    * records of kv_utxo_stats / kv_utxo_rehash, and the export walk's per-entry
    * script references */
   DeviceBuf d_tbl_rec, d_exp_refs;
+  /* undo journal (kv_utxo_journal_kernels.hip): oldest record first; tokens
+   * only grow. d_jrn_rec is the capture launch's copy-back record. */
+  std::deque<JournalRecord> journal;
+  uint64_t next_token = 1;
+  DeviceBuf d_jrn_rec;
+  double last_revert_ms = 0.0; /* kernel_ms of the last kv_utxo_revert */
   /* split Schnorr verify (launch_schnorr_verify): the ladder kernel's R limbs
    * and pre-status, 121 B per signature. One split verify is in flight per
    * context at a time (ctx->mu held, every caller syncs before the next). */
@@ -1763,6 +1792,7 @@ extern "C" int kv_utxo_reset(kv_ctx *ctx, uint64_t capacity) {
   uint64_t cap = 64;
   while (cap < capacity * 2) cap <<= 1; /* ≤50% load factor */
   ctx->utxo_cap = 0;
+  ctx->journal.clear(); /* undo records of the set that goes away */
   if (ctx->d_utxo.alloc(cap * sizeof(kv::utxo_slot))) return -2;
   ctx->utxo_cap = cap;
   HIP_CHECK(hipMemsetAsync(ctx->d_utxo.p, 0, cap * sizeof(kv::utxo_slot), ctx->stream));
@@ -1784,8 +1814,28 @@ static int utxo_stage(kv_ctx *ctx, const uint8_t *outpoints, const uint8_t *valu
   return 0;
 }
 
+/* a (start, stop) pair of timing events that cannot leak on an early return */
+struct EventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~EventPair() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  hipError_t init() {
+    hipError_t e = hipEventCreate(&a);
+    return e == hipSuccess ? hipEventCreate(&b) : e;
+  }
+  /* after a synchronisation of the stream both were recorded on */
+  double ms() const {
+    float v = 0.f;
+    return hipEventElapsedTime(&v, a, b) == hipSuccess ? (double)v : 0.0;
+  }
+};
+
+/* `timed` (optional, initialised by the caller) brackets the launch */
 static int utxo_upsert_nolock(kv_ctx *ctx, const uint8_t *outpoints,
-                              const uint8_t *entries64, size_t n) {
+                              const uint8_t *entries64, size_t n,
+                              const EventPair *timed = nullptr) {
   if (!ctx->d_utxo.p) {
     set_error("kv_utxo_upsert: call kv_utxo_reset first");
     return -1;
@@ -1795,10 +1845,12 @@ static int utxo_upsert_nolock(kv_ctx *ctx, const uint8_t *outpoints,
   if (ctx->d_utxo_fail.ensure(4)) return -2;
   int *d_fail = ctx->d_utxo_fail.as<int>();
   HIP_CHECK(hipMemsetAsync(d_fail, 0, 4, ctx->stream));
+  if (timed) HIP_CHECK(hipEventRecord(timed->a, ctx->stream));
   hipLaunchKernelGGL(kv::kv_utxo_upsert_kernel, dim3(((uint32_t)n + 255) / 256),
                      dim3(256), 0, ctx->stream, ctx->table(), ctx->utxo_cap - 1,
                      ctx->d_op_in.as<uint8_t>(), ctx->d_val_in.as<uint8_t>(),
                      (unsigned long long)n, d_fail);
+  if (timed) HIP_CHECK(hipEventRecord(timed->b, ctx->stream));
   int fail = 0;
   HIP_CHECK(hipMemcpyAsync(&fail, d_fail, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -1831,17 +1883,11 @@ static int arena_reserve(kv_ctx *ctx, uint64_t need) {
   return 0;
 }
 
-/* general upsert: spk_len > 36 entries spill their scripts to the arena
- * (bump-allocated; spans leak on remove until kv_utxo_reset or kv_utxo_rehash
- * — documented) */
-static int utxo_upsert_spk_nolock(kv_ctx *ctx, const uint8_t *outpoints,
-                                  const uint8_t *entries64, const uint8_t *spk_blob,
-                                  size_t spk_blob_len, size_t n) {
-  if (!ctx->d_utxo.p) {
-    set_error("kv_utxo_upsert_spk: call kv_utxo_reset first");
-    return -1;
-  }
-  uint64_t long_total = 0;
+/* the argument rules of kv_utxo_upsert_spk: no script above KV_UTXO_MAX_SPK,
+ * and spk_blob holds the long ones. *long_total = their bytes. */
+static int utxo_spk_args_check(const uint8_t *entries64, size_t spk_blob_len, size_t n,
+                               uint64_t *long_total) {
+  *long_total = 0;
   for (size_t i = 0; i < n; i++) {
     uint32_t spk_len;
     memcpy(&spk_len, entries64 + i * 64 + 20, 4);
@@ -1850,15 +1896,31 @@ static int utxo_upsert_spk_nolock(kv_ctx *ctx, const uint8_t *outpoints,
         set_error("kv_utxo_upsert_spk: spk exceeds KV_UTXO_MAX_SPK");
         return -1;
       }
-      long_total += spk_len;
+      *long_total += spk_len;
     }
   }
-  if (long_total > spk_blob_len) {
+  if (*long_total > spk_blob_len) {
     set_error("kv_utxo_upsert_spk: spk_blob shorter than the long entries");
     return -1;
   }
+  return 0;
+}
+
+/* general upsert: spk_len > 36 entries spill their scripts to the arena
+ * (bump-allocated; spans leak on remove until kv_utxo_reset or kv_utxo_rehash
+ * — documented) */
+static int utxo_upsert_spk_nolock(kv_ctx *ctx, const uint8_t *outpoints,
+                                  const uint8_t *entries64, const uint8_t *spk_blob,
+                                  size_t spk_blob_len, size_t n,
+                                  const EventPair *timed = nullptr) {
+  if (!ctx->d_utxo.p) {
+    set_error("kv_utxo_upsert_spk: call kv_utxo_reset first");
+    return -1;
+  }
+  uint64_t long_total = 0;
+  if (utxo_spk_args_check(entries64, spk_blob_len, n, &long_total)) return -1;
   if (long_total == 0)
-    return utxo_upsert_nolock(ctx, outpoints, entries64, n);
+    return utxo_upsert_nolock(ctx, outpoints, entries64, n, timed);
   int rc = arena_reserve(ctx, long_total);
   if (rc) return rc;
   uint64_t base = ctx->arena_head;
@@ -1882,7 +1944,7 @@ static int utxo_upsert_spk_nolock(kv_ctx *ctx, const uint8_t *outpoints,
     memset(e + 28, 0, 32);
     off += spk_len;
   }
-  return utxo_upsert_nolock(ctx, outpoints, ents.data(), n);
+  return utxo_upsert_nolock(ctx, outpoints, ents.data(), n, timed);
 }
 
 extern "C" int kv_utxo_upsert_spk(kv_ctx *ctx, const uint8_t *outpoints,
@@ -2543,7 +2605,257 @@ extern "C" int kv_utxo_export_chunk(kv_ctx *ctx, uint64_t *cursor, size_t max_en
   return 0;
 }
 
+/* ---------------- undo journal (kv_utxo_journal_kernels.hip) -----------------
+ * ⇔ the stored chain-block diffs of calculate_utxo_state_relatively
+ * (processor.rs:393-437): kv_utxo_apply_diff ⇔ write_diff_batch
+ * (utxo_set.rs:107-112) with the inverse kept, kv_utxo_revert ⇔
+ * with_diff_in_place(as_reversed) (processor.rs:410, utxo_diff.rs:71). */
 
+/* are the na + nb outpoints distinct? A host-side open-addressing set of row
+ * numbers, hashed like the table. */
+static bool ops_distinct(const uint8_t *a, size_t na, const uint8_t *b, size_t nb) {
+  const size_t n = na + nb;
+  if (n < 2) return true;
+  size_t cap = 16;
+  while (cap < 2 * n) cap <<= 1;
+  std::vector<uint32_t> rows(cap, 0); /* row + 1; 0 = free */
+  auto at = [&](size_t i) { return i < na ? a + i * 36 : b + (i - na) * 36; };
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t *op = at(i);
+    uint64_t h;
+    uint32_t idx;
+    memcpy(&h, op, 8);
+    memcpy(&idx, op + 32, 4);
+    h ^= 0x9e3779b97f4a7c15ULL * (idx + 1);
+    size_t slot = (size_t)(h ^ (h >> 32)) & (cap - 1);
+    for (; rows[slot]; slot = (slot + 1) & (cap - 1))
+      if (!memcmp(at(rows[slot] - 1), op, 36)) return false;
+    rows[slot] = (uint32_t)i + 1;
+  }
+  return true;
+}
+
+/* caller holds ctx->mu. Plays the newest record back (see kv_utxo_revert) and
+ * pops it. */
+static int journal_revert_nolock(kv_ctx *ctx, uint64_t token) {
+  if (ctx->journal.empty() || ctx->journal.back().token != token) {
+    set_error("kv_utxo_revert: not the newest unreverted record");
+    return -1;
+  }
+  JournalRecord &r = ctx->journal.back();
+  const size_t n = r.n();
+  const uint64_t base = ctx->arena_head;
+  EventPair ev;
+  HIP_CHECK(ev.init());
+  if (r.blob_bytes) {
+    if (base + r.blob_bytes > 0xffffffffULL) {
+      set_error("kv_utxo_revert: arena exceeds a u32 offset; kv_utxo_rehash first");
+      return -3;
+    }
+    int rc = arena_reserve(ctx, r.blob_bytes);
+    if (rc) return rc;
+  }
+  if (ctx->d_utxo_fail.ensure(4)) return -2;
+  int *d_fail = ctx->d_utxo_fail.as<int>();
+  int fail = 0;
+  HIP_CHECK(hipEventRecord(ev.a, ctx->stream));
+  if (r.blob_bytes)
+    HIP_CHECK(hipMemcpyAsync(ctx->d_arena.as<uint8_t>() + base, r.blob.p, r.blob_bytes,
+                             hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_CHECK(hipMemsetAsync(d_fail, 0, 4, ctx->stream));
+  if (r.n_added)
+    hipLaunchKernelGGL(kv::kv_utxo_journal_unadd_kernel,
+                       dim3(((uint32_t)r.n_added + 255) / 256), dim3(256), 0,
+                       ctx->stream, ctx->table(), ctx->utxo_cap - 1,
+                       (const uint8_t *)r.keys(),
+                       (const unsigned long long *)r.found(),
+                       (unsigned long long)r.n_removed, (unsigned long long)n);
+  if (n)
+    hipLaunchKernelGGL(kv::kv_utxo_journal_restore_kernel,
+                       dim3(((uint32_t)n + 255) / 256), dim3(256), 0, ctx->stream,
+                       ctx->table(), ctx->utxo_cap - 1, (const uint8_t *)r.keys(),
+                       (const uint8_t *)r.vals(), (const unsigned long long *)r.found(),
+                       (unsigned long long)n, base, r.blob_bytes, base + r.blob_bytes,
+                       d_fail);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(ev.b, ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(&fail, d_fail, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  ctx->arena_head = base + r.blob_bytes; /* restored values refer to these bytes */
+  ctx->last_revert_ms = ev.ms();
+  if (fail) {
+    set_error("kv_utxo_revert: table full (the set is not in the state the apply "
+              "left it in)");
+    return -3;
+  }
+  ctx->journal.pop_back();
+  return 0;
+}
+
+/* caller holds ctx->mu; see kv_utxo_apply_diff */
+static int journal_apply_nolock(kv_ctx *ctx, const uint8_t *removed_ops, size_t n_removed,
+                                const uint8_t *added_ops, const uint8_t *added_entries64,
+                                const uint8_t *spk_blob, size_t spk_blob_len,
+                                size_t n_added, kv_utxo_diff_result *res_out,
+                                uint64_t *undo_token_out) {
+  if (!undo_token_out || (n_removed && !removed_ops) ||
+      (n_added && (!added_ops || !added_entries64))) {
+    set_error("kv_utxo_apply_diff: null argument");
+    return -1;
+  }
+  if (!ctx->d_utxo.p) {
+    set_error("kv_utxo_apply_diff: call kv_utxo_reset first");
+    return -1;
+  }
+  if (n_removed > (1u << 30) || n_added > (1u << 30)) {
+    set_error("kv_utxo_apply_diff: diff too large");
+    return -1;
+  }
+  /* every -1 of the upsert that follows the remove is decided here, before
+   * anything changes */
+  uint64_t long_total = 0;
+  if (utxo_spk_args_check(added_entries64, spk_blob_len, n_added, &long_total))
+    return -1;
+  if (!ops_distinct(removed_ops, n_removed, added_ops, n_added)) {
+    set_error("kv_utxo_apply_diff: outpoints are not distinct across removed and added");
+    return -1;
+  }
+  JournalRecord r;
+  r.n_removed = n_removed;
+  r.n_added = n_added;
+  const size_t n = r.n();
+  if (n && r.fixed.alloc(r.fixed_bytes())) return -2;
+  if (ctx->d_jrn_rec.ensure(sizeof(kv::journal_rec)) ||
+      ctx->d_gjobs.ensure(n * sizeof(kv::arena_gather_job)))
+    return -2;
+  kv::journal_rec *d_rec = ctx->d_jrn_rec.as<kv::journal_rec>();
+  kv::journal_rec h_rec = {};
+  EventPair ev_cap, ev_copy, ev_up;
+  HIP_CHECK(ev_cap.init());
+  HIP_CHECK(ev_copy.init());
+  HIP_CHECK(ev_up.init());
+
+  /* capture (and tombstone the removed side): one launch, one 32 B record
+   * back, one synchronisation */
+  if (n_removed)
+    HIP_CHECK(hipMemcpyAsync(r.keys(), removed_ops, n_removed * 36,
+                             hipMemcpyHostToDevice, ctx->stream));
+  if (n_added)
+    HIP_CHECK(hipMemcpyAsync(r.keys() + n_removed * 36, added_ops, n_added * 36,
+                             hipMemcpyHostToDevice, ctx->stream));
+  HIP_CHECK(hipEventRecord(ev_cap.a, ctx->stream));
+  HIP_CHECK(hipMemsetAsync(d_rec, 0, sizeof(kv::journal_rec), ctx->stream));
+  if (n) {
+    hipLaunchKernelGGL(kv::kv_utxo_journal_capture_kernel,
+                       dim3(((uint32_t)n + 255) / 256), dim3(256), 0, ctx->stream,
+                       ctx->table(), ctx->utxo_cap - 1, (const uint8_t *)r.keys(),
+                       (unsigned long long)n, (unsigned long long)n_removed,
+                       ctx->arena_head, r.vals(), r.found(),
+                       ctx->d_gjobs.as<kv::arena_gather_job>(), (uint32_t)n, d_rec);
+    HIP_CHECK(hipGetLastError());
+  }
+  HIP_CHECK(hipEventRecord(ev_cap.b, ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(&h_rec, d_rec, sizeof(kv::journal_rec), hipMemcpyDeviceToHost,
+                           ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  double ms = ev_cap.ms();
+
+  /* the record's own copy of the long scripts it captured, one block a script */
+  r.blob_bytes = h_rec.blob_bytes;
+  if (r.blob_bytes) {
+    if (r.blob.alloc(r.blob_bytes)) return -2;
+    HIP_CHECK(hipEventRecord(ev_copy.a, ctx->stream));
+    hipLaunchKernelGGL(kv::kv_arena_copy_jobs_kernel,
+                       dim3(std::min<uint32_t>(h_rec.n_jobs, (uint32_t)n)), dim3(256), 0,
+                       ctx->stream, ctx->d_arena.as<const uint8_t>(),
+                       ctx->d_gjobs.as<const kv::arena_gather_job>(),
+                       (const uint32_t *)&d_rec->n_jobs, (uint32_t)n,
+                       r.blob.as<uint8_t>());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev_copy.b, ctx->stream));
+  }
+  int rc = 0;
+  if (h_rec.fail) {
+    set_error("kv_utxo_apply_diff: a table entry's script reference is out of range");
+    rc = -3;
+  }
+  /* the diff's upsert; it ends in a synchronisation, which the script copy
+   * needs too */
+  if (!rc && n_added)
+    rc = utxo_upsert_spk_nolock(ctx, added_ops, added_entries64, spk_blob, spk_blob_len,
+                                n_added, &ev_up);
+  else
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (rc && rc != -3) return rc; /* a HIP error: nothing more can be done */
+  if (r.blob_bytes) ms += ev_copy.ms();
+  if (!rc && n_added) ms += ev_up.ms();
+
+  r.token = ctx->next_token++;
+  const uint64_t token = r.token, bytes = r.device_bytes();
+  ctx->journal.push_back(std::move(r));
+  if (rc) {
+    /* failure atomicity: undo what was done from the record just captured */
+    const std::string why = g_last_error;
+    int rr = journal_revert_nolock(ctx, token);
+    if (rr) {
+      set_error((why + "; undoing the partial diff failed too: record " +
+                 std::to_string(token) + " kept")
+                    .c_str());
+      return rr;
+    }
+    set_error(why.c_str());
+    return rc;
+  }
+  if (res_out) {
+    res_out->n_removed_missing = h_rec.n_removed_missing;
+    res_out->n_added_overwrote = h_rec.n_added_overwrote;
+    res_out->journal_bytes = bytes;
+    res_out->kernel_ms = ms;
+  }
+  *undo_token_out = token;
+  return 0;
+}
+
+extern "C" int kv_utxo_apply_diff(kv_ctx *ctx, const uint8_t *removed_ops,
+                                  size_t n_removed, const uint8_t *added_ops,
+                                  const uint8_t *added_entries64, const uint8_t *spk_blob,
+                                  size_t spk_blob_len, size_t n_added,
+                                  kv_utxo_diff_result *res_out,
+                                  uint64_t *undo_token_out) {
+  KV_ENTER(ctx);
+  return journal_apply_nolock(ctx, removed_ops, n_removed, added_ops, added_entries64,
+                              spk_blob, spk_blob_len, n_added, res_out, undo_token_out);
+}
+
+extern "C" int kv_utxo_revert(kv_ctx *ctx, uint64_t token) {
+  KV_ENTER(ctx);
+  return journal_revert_nolock(ctx, token);
+}
+
+extern "C" int kv_utxo_journal_drop(kv_ctx *ctx, uint64_t upto_token) {
+  KV_ENTER(ctx);
+  /* no record is in use on the stream: every apply and revert ends synchronised */
+  while (!ctx->journal.empty() && ctx->journal.front().token <= upto_token)
+    ctx->journal.pop_front();
+  return 0;
+}
+
+extern "C" int kv_utxo_journal_stats(kv_ctx *ctx, kv_utxo_journal_info *out) {
+  if (!ctx || !out) {
+    set_error("kv_utxo_journal_stats: null argument");
+    return -1;
+  }
+  KV_ENTER(ctx);
+  memset(out, 0, sizeof(*out));
+  out->n_records = ctx->journal.size();
+  if (!ctx->journal.empty()) {
+    out->oldest_token = ctx->journal.front().token;
+    out->newest_token = ctx->journal.back().token;
+  }
+  for (const JournalRecord &r : ctx->journal) out->device_bytes += r.device_bytes();
+  out->last_revert_kernel_ms = ctx->last_revert_ms;
+  return 0;
+}
 
 static int populate_blob_nolock(kv_ctx *ctx, const uint8_t *blob, size_t blob_len,
                                 std::vector<kvhost::HTx> &txs, int n_txs,
@@ -2897,13 +3209,57 @@ static int populate_blob_nolock(kv_ctx *ctx, const uint8_t *blob, size_t blob_le
   return 0;
 }
 
-extern "C" int kv_validate_block_utxo(kv_ctx *ctx, const uint8_t *blob,
-                                      size_t blob_len, uint64_t pov_daa_score,
-                                      uint64_t block_daa_score, uint32_t flags,
-                                      int apply_diff, int32_t *tx_codes_out,
-                                      uint64_t *fees_out,
-                                      uint8_t *muhash_partial_out) {
-  KV_ENTER(ctx);
+/* the diff of a validated block ⇔ utxo_diff.rs:224 add_transaction per accepted
+ * tx: its inputs' outpoints to remove, its outputs to upsert (in the input
+ * format of kv_utxo_upsert_spk) */
+struct BlockDiff {
+  std::vector<uint8_t> del_ops, add_ops, add_ents, add_spk;
+};
+
+static int build_block_diff(const vector<HTx> &txs, int n_txs, const int32_t *tx_codes,
+                            uint64_t block_daa_score, BlockDiff &d) {
+  for (int t = 0; t < n_txs; t++) {
+    const HTx &tx = txs[t];
+    if (tx_codes[t] != 0) continue;
+    for (auto &in : tx.inputs) {
+      uint8_t op[36];
+      memcpy(op, in.prev_tx_id, 32);
+      memcpy(op + 32, &in.prev_index, 4);
+      d.del_ops.insert(d.del_ops.end(), op, op + 36);
+    }
+    for (uint32_t i = 0; i < tx.outputs.size(); i++) {
+      const HOutput &o = tx.outputs[i];
+      if (o.spk_len > KV_UTXO_MAX_SPK) {
+        set_error("kv_validate_block_utxo: created spk exceeds KV_UTXO_MAX_SPK");
+        return -4;
+      }
+      d.add_ops.insert(d.add_ops.end(), tx.tx_id, tx.tx_id + 32);
+      const uint8_t *ix = (const uint8_t *)&i;
+      d.add_ops.insert(d.add_ops.end(), ix, ix + 4);
+      uint8_t e[64] = {0};
+      memcpy(e, &o.value, 8);
+      memcpy(e + 8, &block_daa_score, 8);
+      /* flags: coinbase txs never enter this path → bit0 = 0 */
+      memcpy(e + 18, &o.spk_version, 2);
+      memcpy(e + 20, &o.spk_len, 4);
+      if (o.spk_len <= 36)
+        memcpy(e + 24, o.spk, o.spk_len);
+      else /* out-of-line: bytes go to the arena via upsert_spk */
+        d.add_spk.insert(d.add_spk.end(), o.spk, o.spk + o.spk_len);
+      d.add_ents.insert(d.add_ents.end(), e, e + 64);
+    }
+  }
+  return 0;
+}
+
+/* caller holds ctx->mu. undo_token_out != NULL: the diff is applied through
+ * the journal (and apply_diff is taken as set). */
+static int validate_block_utxo_nolock(kv_ctx *ctx, const uint8_t *blob, size_t blob_len,
+                                      uint64_t pov_daa_score, uint64_t block_daa_score,
+                                      uint32_t flags, int apply_diff,
+                                      int32_t *tx_codes_out, uint64_t *fees_out,
+                                      uint8_t *muhash_partial_out,
+                                      uint64_t *undo_token_out) {
   if (!ctx->d_utxo.p) {
     set_error("kv_validate_block_utxo: call kv_utxo_reset first");
     return -1;
@@ -2921,52 +3277,56 @@ extern "C" int kv_validate_block_utxo(kv_ctx *ctx, const uint8_t *blob,
   rc = validate_block_impl(ctx, pop.data(), pop.size(), pov_daa_score,
                            block_daa_score, flags, tx_codes_out, fees_out,
                            muhash_partial_out, pre_codes.data());
-  if (rc || !apply_diff) return rc;
+  if (rc || (!apply_diff && !undo_token_out)) return rc;
 
   /* diff apply for accepted txs: remove spent, upsert created */
-  std::vector<uint8_t> del_ops, add_ops, add_ents, add_spk;
-  for (int t = 0; t < n_txs; t++) {
-    const HTx &tx = txs[t];
-    if (tx_codes_out[t] != 0) continue;
-    for (auto &in : tx.inputs) {
-      uint8_t op[36];
-      memcpy(op, in.prev_tx_id, 32);
-      memcpy(op + 32, &in.prev_index, 4);
-      del_ops.insert(del_ops.end(), op, op + 36);
-    }
-    for (uint32_t i = 0; i < tx.outputs.size(); i++) {
-      const HOutput &o = tx.outputs[i];
-      if (o.spk_len > KV_UTXO_MAX_SPK) {
-        set_error("kv_validate_block_utxo: created spk exceeds KV_UTXO_MAX_SPK");
-        return -4;
-      }
-      add_ops.insert(add_ops.end(), tx.tx_id, tx.tx_id + 32);
-      const uint8_t *ix = (const uint8_t *)&i;
-      add_ops.insert(add_ops.end(), ix, ix + 4);
-      uint8_t e[64] = {0};
-      memcpy(e, &o.value, 8);
-      memcpy(e + 8, &block_daa_score, 8);
-      /* flags: coinbase txs never enter this path → bit0 = 0 */
-      memcpy(e + 18, &o.spk_version, 2);
-      memcpy(e + 20, &o.spk_len, 4);
-      if (o.spk_len <= 36)
-        memcpy(e + 24, o.spk, o.spk_len);
-      else /* out-of-line: bytes go to the arena via upsert_spk below */
-        add_spk.insert(add_spk.end(), o.spk, o.spk + o.spk_len);
-      add_ents.insert(add_ents.end(), e, e + 64);
-    }
-  }
-  if (!del_ops.empty()) {
-    rc = utxo_remove_nolock(ctx, del_ops.data(), del_ops.size() / 36);
+  BlockDiff d;
+  rc = build_block_diff(txs, n_txs, tx_codes_out, block_daa_score, d);
+  if (rc) return rc;
+  if (undo_token_out)
+    return journal_apply_nolock(ctx, d.del_ops.data(), d.del_ops.size() / 36,
+                                d.add_ops.data(), d.add_ents.data(), d.add_spk.data(),
+                                d.add_spk.size(), d.add_ops.size() / 36, nullptr,
+                                undo_token_out);
+  if (!d.del_ops.empty()) {
+    rc = utxo_remove_nolock(ctx, d.del_ops.data(), d.del_ops.size() / 36);
     if (rc) return rc;
   }
-  if (!add_ops.empty()) {
-    rc = utxo_upsert_spk_nolock(ctx, add_ops.data(), add_ents.data(),
-                                add_spk.data(), add_spk.size(),
-                                add_ops.size() / 36);
+  if (!d.add_ops.empty()) {
+    rc = utxo_upsert_spk_nolock(ctx, d.add_ops.data(), d.add_ents.data(),
+                                d.add_spk.data(), d.add_spk.size(),
+                                d.add_ops.size() / 36);
     if (rc) return rc;
   }
   return 0;
+}
+
+extern "C" int kv_validate_block_utxo(kv_ctx *ctx, const uint8_t *blob,
+                                      size_t blob_len, uint64_t pov_daa_score,
+                                      uint64_t block_daa_score, uint32_t flags,
+                                      int apply_diff, int32_t *tx_codes_out,
+                                      uint64_t *fees_out,
+                                      uint8_t *muhash_partial_out) {
+  KV_ENTER(ctx);
+  return validate_block_utxo_nolock(ctx, blob, blob_len, pov_daa_score, block_daa_score,
+                                    flags, apply_diff, tx_codes_out, fees_out,
+                                    muhash_partial_out, nullptr);
+}
+
+extern "C" int kv_validate_block_utxo_undo(kv_ctx *ctx, const uint8_t *blob,
+                                           size_t blob_len, uint64_t pov_daa_score,
+                                           uint64_t block_daa_score, uint32_t flags,
+                                           int32_t *tx_codes_out, uint64_t *fees_out,
+                                           uint8_t *muhash_partial_out,
+                                           uint64_t *undo_token_out) {
+  KV_ENTER(ctx);
+  if (!undo_token_out) {
+    set_error("kv_validate_block_utxo_undo: null undo_token_out");
+    return -1;
+  }
+  return validate_block_utxo_nolock(ctx, blob, blob_len, pov_daa_score, block_daa_score,
+                                    flags, 1, tx_codes_out, fees_out,
+                                    muhash_partial_out, undo_token_out);
 }
 
 /* ---- direct mass-vector test exports (tests/golden/mass.json, extracted from

@@ -67,16 +67,13 @@ __device__ __forceinline__ int key_eq(const uint8_t *a, const uint8_t *b) {
  * live key's chain by a prior remove must not be claimed until the key is
  * known absent, or the table would hold two READY slots for one outpoint and a
  * later remove would resurrect the stale one. We remember the first tombstone
- * seen and claim it only after reaching the chain's end without a match. */
-extern "C" __global__ void kv_utxo_upsert_kernel(utxo_slot *table, uint64_t cap_mask,
-                                                 const uint8_t *__restrict__ outpoints,
-                                                 const uint8_t *__restrict__ values,
-                                                 unsigned long long n,
-                                                 int *__restrict__ fail_flag) {
-  unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint8_t *key = outpoints + i * 36;
-  const uint8_t *val = values + i * 64;
+ * seen and claim it only after reaching the chain's end without a match.
+ *
+ * The lane's work is a function of its own: kv_utxo_upsert_kernel runs it on
+ * staged rows, kv_utxo_journal_restore_kernel (kv_utxo_journal_kernels.hip) on
+ * the rows of an undo record. Returns 0, or 1 when the table is full. */
+__device__ __forceinline__ int utxo_upsert_lane(utxo_slot *table, uint64_t cap_mask,
+                                                const uint8_t *key, const uint8_t *val) {
   const uint64_t home = op_hash(key) & cap_mask;
   for (;;) { /* restart only on a lost claim race (rare) */
     uint64_t cand = ~0ULL; /* first tombstone seen this scan */
@@ -94,7 +91,7 @@ extern "C" __global__ void kv_utxo_upsert_kernel(utxo_slot *table, uint64_t cap_
         if (st == KV_SLOT_READY) {
           if (key_eq(s->key, key)) { /* overwrite value (upsert semantics) */
             for (int k = 0; k < 64; k++) s->value[k] = val[k];
-            return;
+            return 0;
           }
           continue;
         }
@@ -120,16 +117,27 @@ extern "C" __global__ void kv_utxo_upsert_kernel(utxo_slot *table, uint64_t cap_
           for (int k = 0; k < 64; k++) t->value[k] = val[k];
           __hip_atomic_store(&t->state, KV_SLOT_READY, __ATOMIC_RELEASE,
                              __HIP_MEMORY_SCOPE_AGENT);
-          return;
+          return 0;
         }
         restart = 1; /* another lane took the slot: rescan from home */
         break;
       }
     }
     if (restart) continue;
-    if (fail_flag) *fail_flag = 1; /* table full */
-    return;
+    return 1; /* table full */
   }
+}
+
+extern "C" __global__ void kv_utxo_upsert_kernel(utxo_slot *table, uint64_t cap_mask,
+                                                 const uint8_t *__restrict__ outpoints,
+                                                 const uint8_t *__restrict__ values,
+                                                 unsigned long long n,
+                                                 int *__restrict__ fail_flag) {
+  unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (utxo_upsert_lane(table, cap_mask, outpoints + i * 36, values + i * 64) &&
+      fail_flag)
+    *fail_flag = 1;
 }
 
 extern "C" __global__ void kv_utxo_remove_kernel(utxo_slot *table, uint64_t cap_mask,

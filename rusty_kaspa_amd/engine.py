@@ -34,6 +34,21 @@ class KvUtxoTableStats(ctypes.Structure):
                 ("arena_cap", ctypes.c_uint64)]
 
 
+class KvUtxoDiffResult(ctypes.Structure):
+    _fields_ = [("n_removed_missing", ctypes.c_uint64),
+                ("n_added_overwrote", ctypes.c_uint64),
+                ("journal_bytes", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double)]
+
+
+class KvUtxoJournalInfo(ctypes.Structure):
+    _fields_ = [("n_records", ctypes.c_uint64),
+                ("oldest_token", ctypes.c_uint64),
+                ("newest_token", ctypes.c_uint64),
+                ("device_bytes", ctypes.c_uint64),
+                ("last_revert_kernel_ms", ctypes.c_double)]
+
+
 def load_library() -> ctypes.CDLL:
     if not os.path.exists(_LIB_PATH):
         raise RuntimeError(
@@ -233,6 +248,62 @@ class Engine:
         return (cur.value, ctypes.string_at(ops, 36 * n.value),
                 ctypes.string_at(ents, 64 * n.value),
                 ctypes.string_at(spk, used.value), n.value)
+
+    def utxo_apply_diff(self, removed_ops: bytes, added_ops: bytes = b"",
+                        added_entries64: bytes = b"", spk_blob: bytes = b""):
+        """Remove, then upsert_spk, with the inverse pushed onto the device
+        undo journal (kv_utxo_apply_diff): (token, result), result a dict of
+        n_removed_missing, n_added_overwrote, journal_bytes, kernel_ms.
+        Raises, with the set unchanged, if the call fails."""
+        assert len(removed_ops) % 36 == 0 and len(added_ops) % 36 == 0
+        assert len(added_entries64) == len(added_ops) // 36 * 64
+        res = KvUtxoDiffResult()
+        token = ctypes.c_uint64()
+        rc = self.lib.kv_utxo_apply_diff(
+            ctypes.c_void_p(self.ctx), removed_ops,
+            ctypes.c_size_t(len(removed_ops) // 36), added_ops, added_entries64,
+            spk_blob, ctypes.c_size_t(len(spk_blob)),
+            ctypes.c_size_t(len(added_ops) // 36), ctypes.byref(res),
+            ctypes.byref(token))
+        self._check(rc)
+        return token.value, {name: getattr(res, name) for name, _ in res._fields_}
+
+    def utxo_revert(self, token: int) -> None:
+        """Undo the newest journaled diff and pop its record (kv_utxo_revert).
+        Raises if `token` is not the newest unreverted record."""
+        self._check(self.lib.kv_utxo_revert(ctypes.c_void_p(self.ctx),
+                                            ctypes.c_uint64(token)))
+
+    def utxo_journal_drop(self, upto_token: int) -> None:
+        """Free every undo record with token <= upto_token."""
+        self._check(self.lib.kv_utxo_journal_drop(ctypes.c_void_p(self.ctx),
+                                                  ctypes.c_uint64(upto_token)))
+
+    def utxo_journal_stats(self) -> dict:
+        """What the undo journal holds (kv_utxo_journal_stats): n_records,
+        oldest_token, newest_token (0 when empty), device_bytes, and the
+        kernel_ms of the last revert."""
+        out = KvUtxoJournalInfo()
+        self._check(self.lib.kv_utxo_journal_stats(ctypes.c_void_p(self.ctx),
+                                                   ctypes.byref(out)))
+        return {name: getattr(out, name) for name, _ in out._fields_}
+
+    def validate_block_utxo_undo(self, blob: bytes, n_txs: int, pov_daa: int,
+                                 block_daa: int, flags: int = 2,
+                                 want_muhash: bool = True):
+        """validate_block_utxo(apply_diff=True) whose diff can be reverted:
+        (codes, fees, partial, token)."""
+        codes = (ctypes.c_int32 * n_txs)()
+        fees = (ctypes.c_uint64 * n_txs)()
+        partial = (ctypes.c_uint8 * 768)() if want_muhash else None
+        token = ctypes.c_uint64()
+        rc = self.lib.kv_validate_block_utxo_undo(
+            ctypes.c_void_p(self.ctx), blob, ctypes.c_size_t(len(blob)),
+            ctypes.c_uint64(pov_daa), ctypes.c_uint64(block_daa),
+            ctypes.c_uint32(flags), codes, fees, partial, ctypes.byref(token))
+        self._check(rc)
+        return (list(codes), list(fees),
+                bytes(partial) if want_muhash else None, token.value)
 
     def sig_cache_stats(self):
         out = KvCacheStats()
