@@ -180,55 +180,106 @@ struct fe26 {
 #define KV26_CHECK_MUL_IN(a)
 #endif
 
+/* A fold multiplier the compiler must treat as a run-time value. A plain
+ * power-of-two or R0 << s constant is strength-reduced into a move, a 64-bit
+ * shift and a 64-bit add with carry (three or four VALU instructions); kept
+ * opaque it stays ONE v_mad_u64_u32 with the column as its addend. The empty
+ * asm emits nothing: the constant sits in an SGPR (one scalar move). */
+__device__ __forceinline__ u32 kv26_mulc(u32 c) {
+#ifndef KV_HOST_TEST
+  asm("" : "+s"(c));
+#endif
+  return c;
+}
+
 __device__ __forceinline__ void fe26_reduce19(fe26 &r, const u64 t[19]) {
-  /* Digit-first reduction. Input: the column sums of fe26_mul_inner /
+  /* Half-word reduction. Input: the column sums of fe26_mul_inner /
    * fe26_sqr_inner for operand limbs <= 2^30, so t[k] <= n_k * 2^60 with
    * n_k = min(k + 1, 19 - k) products (t[9] <= 10*2^60 < 2^64, every other
    * column <= 9*2^60). Output: l0, l1 < 2^26, l2 <= 2^26, l3..l8 < 2^26,
    * l9 < 2^22 — magnitude 1 with l2 grazing 2^26 by at most one.
    *
-   * 1. One carry sweep over the HIGH half (bits 26.. of t[9], then columns
-   *    10..18) turns it into 26-bit digits u[0..9] plus a small u[10]:
-   *    high half == sum u[k] * 2^(260 + 26k). Each d <= 9*2^60 + c with
-   *    c < 2^38 (a carry is a 64-bit value >> 26), so d < 2^64; the last carry
-   *    is <= (2^60 + 2^38) >> 26, so u[10] <= 2^8.
-   * 2. 2^260 == R0 + 2^36 (mod p), so digit u[k] lands as u[k]*R0 in column k
-   *    and u[k] << 10 in column k + 1: every fold operand is a 26-bit digit
-   *    and every fold term is < 2^40. u[9] and u[10] reach column 10 again:
-   *    W = (u9 << 10) + u10*R0 + (u10 << 36) < 2^36 + 2^22 + 2^44 < 2^45 is
-   *    folded once more as w0 = W mod 2^26 and w1 = W >> 26 < 2^19 into
-   *    columns 0..2 (terms < 2^40).
-   * 3. One sweep over the LOW half with the fold terms added on the way:
-   *    d <= 9*2^60 + 2^38 (carry) + 4 * 2^40 < 2^64. Column 9 takes only the
-   *    low 26 bits of t[9], so the carry out is cc < 2^15.
-   * 4. Bits 22.. of l9 and cc sit at 2^256 == 2^32 + 977: x < 2^19 + 2^4, so
-   *    x*977 < 2^29 and x << 6 < 2^26 fit u32 on top of a 26-bit digit; a
+   * A 64-bit column already lives in two 32-bit registers, H and L. Columns
+   * are 26 bits apart and 2^32 = 2^26 * 2^6, so H of column j is H * 2^6 in
+   * column j + 1; 2^260 == R0 + 2^36 (mod p), so a value v in column k + 10 is
+   * v*R0 in column k plus v*2^10 in column k + 1. Every step below is one
+   * 32 x 32 -> 64 multiply-add into a column; s[] starts as a copy of t[].
+   *
+   * 1. Upward, j = 9..17: H = s[j] >> 32, s[j] keeps its low half,
+   *    s[j+1] += H * 2^6. H < 2^32, so each add is < 2^38 and every column
+   *    stays <= 9*2^60 + 2^38 (s[10] <= 9*2^60 + 2^38 takes the H of t[9]).
+   * 2. Top: s[18] <= 2^60 + 2^38, so H18 <= 2^28 + 2^6 < 2^29. H18 * 2^6 sits
+   *    in column 19 = column 9 of the folded half: s[9] += H18 * (R0 << 6)
+   *    (< 2^49), and its 2^36 part, H18 * 2^42 in column 9 = H18 * 2^16 in
+   *    column 10, folds again: s[0] += H18 * (R0 << 16) (R0 << 16 < 2^30 is a
+   *    u32; the term is < 2^59) and H18 * 2^52 = H18 in column 2.
+   * 3. Fold, j = 10..18, k = j - 10, L = s[j] < 2^32: s[k] += L * R0 (< 2^46),
+   *    s[k+1] += L * 2^10 (< 2^42).
+   * 4. Column 9 is now < 2^32 + 2^49 + 2^42 < 2^50: H9 < 2^18 goes, as
+   *    H9 * 2^6 in column 10, to s[0] += H9 * (R0 << 6) (< 2^38) and
+   *    s[1] += H9 * 2^16 (< 2^34); s[9] keeps its low half.
+   *    Worst cases after all folds: s[0] <= 2^60 + 2^59 + 2^46 + 2^38;
+   *    s[k], 1 <= k <= 8, <= n_k*2^60 + 2^46 + 2^42 + 2^34 + 2^29
+   *    <= 9*2^60 + 2^47; s[9] < 2^32. All <= n_k*2^60 + 2^59.
+   * 5. One 26-bit sweep over columns 0..9: d <= 9*2^60 + 2^59 + carry with
+   *    carry < 2^38, so d < 2^64. d9 < 2^32 + 2^38: the carry out is
+   *    cc < 2^13.
+   * 6. Bits 22.. of l9 and cc sit at 2^256 == 2^32 + 977: x < 2^17 + 2^4, so
+   *    x*977 < 2^27 and x << 6 < 2^24 fit u32 on top of a 26-bit digit; a
    *    three-limb ripple leaves l0, l1 < 2^26 and adds at most 1 to l2. */
-  u32 u[11];
-  u64 c = t[9] >> 26;
+  const u32 c6 = kv26_mulc(1u << 6), c10 = kv26_mulc(1u << 10),
+            c16 = kv26_mulc(1u << 16), r0 = kv26_mulc((u32)KV26_R0),
+            r6 = kv26_mulc((u32)KV26_R0 << 6),
+            r16 = kv26_mulc((u32)KV26_R0 << 16);
+  u64 s[19];
 #pragma unroll
-  for (int k = 0; k < 9; k++) {
-    u64 d = t[k + 10] + c;
-    u[k] = (u32)d & KV26_M;
-    c = d >> 26;
+  for (int k = 0; k < 19; k++) {
+    s[k] = t[k];
+#ifdef KV_HOST_TEST
+    assert(s[k] <= (u64)(k < 10 ? k + 1 : 19 - k) << 60);
+#endif
   }
-  u[9] = (u32)c & KV26_M;
-  u[10] = (u32)(c >> 26);
-  u64 W = ((u64)u[9] << 10) + (u64)u[10] * KV26_R0 + ((u64)u[10] << 36);
-  u32 w0 = (u32)W & KV26_M, w1 = (u32)(W >> 26);
+#pragma unroll
+  for (int j = 9; j < 18; j++) {
+    u32 h = (u32)(s[j] >> 32);
+    s[j] = (u32)s[j];
+    s[j + 1] += (u64)h * c6;
+#ifdef KV_HOST_TEST
+    assert(s[j + 1] <= ((u64)(18 - j) << 60) + ((u64)1 << 38));
+#endif
+  }
+  u32 h18 = (u32)(s[18] >> 32);
+  s[18] = (u32)s[18];
+  s[9] += (u64)h18 * r6;
+  s[0] += (u64)h18 * r16;
+  s[2] += h18;
+#pragma unroll
+  for (int j = 10; j < 19; j++) {
+    u32 lo = (u32)s[j];
+    s[j - 10] += (u64)lo * r0;
+    s[j - 9] += (u64)lo * c10;
+  }
+  u32 h9 = (u32)(s[9] >> 32);
+#ifdef KV_HOST_TEST
+  assert(h18 < (1u << 29) && s[9] < ((u64)1 << 50) && h9 < (1u << 18));
+#endif
+  s[9] = (u32)s[9];
+  s[0] += (u64)h9 * r6;
+  s[1] += (u64)h9 * c16;
   u64 cc = 0;
 #pragma unroll
   for (int k = 0; k < 10; k++) {
-    u64 d = (k == 9 ? (t[9] & KV26_M) : t[k]) + cc + (u64)u[k] * KV26_R0;
-    if (k >= 1) d += (u64)u[k - 1] << 10;
-    if (k == 0) d += (u64)w0 * KV26_R0;
-    if (k == 1) d += ((u64)w0 << 10) + (u64)w1 * KV26_R0;
-    if (k == 2) d += (u64)w1 << 10;
+#ifdef KV_HOST_TEST
+    assert(k == 9 ? s[9] < ((u64)1 << 32)
+                  : s[k] <= ((u64)(k + 1) << 60) + ((u64)1 << 59));
+    assert(cc < ((u64)1 << 38));
+#endif
+    u64 d = s[k] + cc;
     r.l[k] = (u32)d & KV26_M;
     cc = d >> 26;
   }
 #ifdef KV_HOST_TEST
-  assert(u[10] <= (1u << 8) && W < ((u64)1 << 45) && cc < (1u << 15));
+  assert(cc < (1u << 13));
 #endif
   /* keep the top limb 22-bit (the magnitude convention scales l9 by 2^22) */
   u32 x = (r.l[9] >> 22) + ((u32)cc << 4);
