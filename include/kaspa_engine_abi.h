@@ -106,6 +106,13 @@ extern "C" {
 #define KV_ERR_BODY_DUP_TX 10
 #define KV_ERR_BODY_DOUBLE_SPEND 11
 #define KV_ERR_BODY_CHAINED 12
+/* covenant bindings (TxRuleError::CovenantsError ⇔ CovenantsContext::from_tx,
+ * crypto/txscript/src/covenants.rs:101-163), checked after the sequence lock
+ * and before any script work (tx_validation_in_utxo_context.rs:58) */
+#define KV_ERR_COVENANT_AUTH_INPUT 13 /* AuthInputOutOfBounds: an output's
+                                         authorizing_input >= input count */
+#define KV_ERR_COVENANT_GENESIS_ID 14 /* WrongGenesisCovenantId: a genesis group's
+                                         id is not hashing::covenant_id of it */
 #define KV_ERR_BAD_BLOB 90
 #define KV_ERR_SIGNATURE_INVALID_BASE 100
 #define KV_ERR_SIGNATURE_EMPTY_BASE 200
@@ -256,16 +263,29 @@ int kv_g_comb_fetch(kv_ctx *ctx, uint32_t first, uint32_t count, uint8_t *out64)
  * byte offset. Arena space is bump-allocated; removing an entry leaks its
  * arena span until the next kv_utxo_reset or kv_utxo_rehash (documented trade:
  * non-standard outputs are rare; the arena compacts on reset and on rehash,
- * and kv_utxo_stats reports the leaked bytes). */
+ * and kv_utxo_stats reports the leaked bytes).
+ *
+ * Covenant ids (UtxoEntry::covenant_id): an entry that carries one has flags
+ * bit2 (KV_UTXO_F_COVENANT) and the 32-byte id in bytes 28..60 of the record.
+ * Its script ALWAYS travels out of line, whatever its length (an empty one
+ * included): in every spk blob below (kv_utxo_upsert_spk, kv_utxo_import_chunk,
+ * kv_utxo_apply_diff in; kv_utxo_export_chunk, kv_utxo_lookup_spk out) it sits
+ * in entry order among the scripts longer than 36 bytes. On input bytes 24..28
+ * of such a record are ignored. In the table the value also has
+ * KV_UTXO_F_SPK_ARENA, the arena offset in bytes 24..28 and zeros in 60..64;
+ * the arena span is exactly spk_len bytes. kv_utxo_upsert (inline only)
+ * refuses the flag with -1. */
 #define KV_UTXO_F_COINBASE 1u
 #define KV_UTXO_F_SPK_ARENA 2u
+#define KV_UTXO_F_COVENANT 4u
 #define KV_UTXO_MAX_SPK 10000u
 int kv_utxo_reset(kv_ctx *ctx, uint64_t capacity);
 /* inline-only upsert: every entry's spk_len must be ≤ 36 */
 int kv_utxo_upsert(kv_ctx *ctx, const uint8_t *outpoints, const uint8_t *entries64,
                    size_t n);
-/* general upsert: entries with spk_len > 36 take their script bytes from
- * spk_blob, concatenated in entry order (total = sum of those spk_lens);
+/* general upsert: entries with spk_len > 36, and covenant entries of any
+ * length, take their script bytes from spk_blob, concatenated in entry order
+ * (total = sum of those spk_lens);
  * the engine stores them in the arena and rewrites the entry in the table
  * with KV_UTXO_F_SPK_ARENA + the arena offset. */
 int kv_utxo_upsert_spk(kv_ctx *ctx, const uint8_t *outpoints,
@@ -288,8 +308,8 @@ int kv_utxo_lookup_spk(kv_ctx *ctx, const uint8_t *outpoints, size_t n,
  * An entry's element is MuHash::from_utxo over write_utxo
  * (consensus/core/src/muhash.rs:55-69): tx_id ‖ index u32 ‖ daa_score u64 ‖
  * amount u64 ‖ is_coinbase u8 ‖ spk_version u16 ‖ spk_len u64 ‖ spk. Arena
- * scripts are hashed in place. The table stores no covenant ids (covenant
- * outputs are KV_ERR_BAD_BLOB on the table path), so none is hashed. */
+ * scripts are hashed in place. An entry with KV_UTXO_F_COVENANT appends its
+ * 32-byte covenant id after the script (muhash.rs:66-67). */
 
 /* ⇔ MuHash over every live entry of the GPU-resident set
  *   (import_pruning_point_utxo_set's multiset, consensus/src/pipeline/
@@ -408,8 +428,9 @@ int kv_utxo_rehash(kv_ctx *ctx, uint64_t capacity, double *kernel_ms /*optional*
  * Output is exactly the input format of kv_utxo_upsert_spk /
  * kv_utxo_import_chunk, so a chunk can be fed straight back: inline entries
  * are copied as stored; an arena entry has KV_UTXO_F_SPK_ARENA cleared and its
- * 36-byte spk field zeroed, and its script bytes are appended to spk_out in
- * entry order (*spk_used = total).
+ * 36-byte spk field zeroed (a covenant entry: bytes 24..28 zeroed,
+ * KV_UTXO_F_COVENANT and the id in 28..60 kept), and its script bytes are
+ * appended to spk_out in entry order (*spk_used = total).
  * spk_cap must be >= KV_UTXO_MAX_SPK (else -1), so one entry always fits. A
  * chunk ends early, with the cursor before the next entry, when that entry's
  * script would not fit; it may also come back short of max_entries — empty

@@ -163,3 +163,77 @@ def strip_utxo_entries(blob: bytes):
         header.append(struct.pack("<I", off))
         off += len(e)
     return b"".join(header + out_txs), seeds
+
+
+KV_UTXO_F_COVENANT = 4  # include/kaspa_engine_abi.h
+
+
+def pack_utxo_entries(entries):
+    """utxo_entry dicts -> (entries64, spk_blob) in the input form of
+    kv_utxo_upsert_spk / kv_utxo_import_chunk / kv_utxo_apply_diff.
+
+    A script of at most 36 bytes is inline. A longer one goes to the spk blob,
+    in entry order. An entry with a covenant_id gets KV_UTXO_F_COVENANT and the
+    id in bytes 28..60, and its script goes to the blob whatever its length.
+    """
+    ents, spks = [], []
+    for u in entries:
+        spk, cid = u["spk"], u["covenant_id"]
+        flags = (1 if u["is_coinbase"] else 0) | (KV_UTXO_F_COVENANT if cid else 0)
+        head = struct.pack("<QQHHI", u["amount"], u["daa_score"], flags,
+                           u["spk_version"], len(spk))
+        if cid:
+            assert len(cid) == 32
+            ents.append(head + bytes(4) + cid + bytes(4))
+            spks.append(spk)
+        elif len(spk) <= 36:
+            ents.append(head + spk.ljust(36, b"\0") + bytes(4))
+        else:
+            ents.append(head + bytes(40))
+            spks.append(spk)
+    return b"".join(ents), b"".join(spks)
+
+
+def strip_utxo_entries_spk(blob: bytes):
+    """strip_utxo_entries for any populated blob: (unpopulated_blob,
+    outpoints, entries64, spk_blob), the last three ready for
+    kv_utxo_upsert_spk (see pack_utxo_entries). Long scripts and covenant ids
+    are kept, which strip_utxo_entries' inline seeds cannot do."""
+    n_txs, = struct.unpack_from("<I", blob, 0)
+    offs = list(struct.unpack_from(f"<{n_txs}I", blob, 4))
+    ops, entries, out_txs = [], [], []
+    for t in range(n_txs):
+        off = offs[t]
+        end = offs[t + 1] if t + 1 < n_txs else len(blob)
+        p = off
+        n_in, = struct.unpack_from("<H", blob, p + 2)
+        payload_len, = struct.unpack_from("<I", blob, p + 36)
+        p += 88 + payload_len
+        chunks = [blob[off:p]]
+        for _ in range(n_in):
+            ops.append(blob[p:p + 36])
+            sig_len, = struct.unpack_from("<I", blob, p + 48)
+            chunks.append(blob[p:p + 52 + sig_len])
+            p += 52 + sig_len
+            amount, daa = struct.unpack_from("<QQ", blob, p)
+            is_cb, has_cov = blob[p + 16], blob[p + 17]
+            spkv, = struct.unpack_from("<H", blob, p + 18)
+            spk_len, = struct.unpack_from("<I", blob, p + 20)
+            p += 24
+            spk = blob[p:p + spk_len]
+            p += spk_len
+            cid = None
+            if has_cov:
+                cid = blob[p:p + 32]
+                p += 32
+            entries.append(utxo_entry(amount, spk, daa, bool(is_cb & 1), spkv, cid))
+            chunks.append(bytes(24))  # zero entry, spk_len 0
+        chunks.append(blob[p:end])  # outputs verbatim
+        out_txs.append(b"".join(chunks))
+    header = [struct.pack("<I", n_txs)]
+    off = 4 + 4 * n_txs
+    for e in out_txs:
+        header.append(struct.pack("<I", off))
+        off += len(e)
+    entries64, spk_blob = pack_utxo_entries(entries)
+    return b"".join(header + out_txs), b"".join(ops), entries64, spk_blob

@@ -1325,12 +1325,16 @@ static void phase1_tx(kv_ctx *ctx, ValidateCall &c, uint32_t t,
       }
     }
   }
-  if (!code)
+  if (!code && tx.version == 0)
     for (auto &o : tx.outputs)
       if (o.has_covenant) {
-        code = KV_ERR_BAD_BLOB; /* covenants out of round-1 scope */
+        /* the v0 wire form has no binding field (CovenantBindingInV0 belongs
+         * to the isolation checks): such a blob cannot come from a node */
+        code = KV_ERR_BAD_BLOB;
         break;
       }
+  /* check_covenant_info (tx_validation_in_utxo_context.rs:58) */
+  if (!code) code = kvh_check_covenant_info(tx);
   c.codes[t] = code;
   c.fees[t] = total_in - total_out;
   if (code || c.flags == KV_FLAGS_SKIP_SCRIPT_CHECKS) return;
@@ -1864,6 +1868,15 @@ static int utxo_upsert_nolock(kv_ctx *ctx, const uint8_t *outpoints,
 extern "C" int kv_utxo_upsert(kv_ctx *ctx, const uint8_t *outpoints,
                               const uint8_t *entries64, size_t n) {
   KV_ENTER(ctx);
+  /* a covenant id lives where an inline script would: kv_utxo_upsert_spk */
+  for (size_t i = 0; i < n; i++) {
+    uint16_t flags;
+    memcpy(&flags, entries64 + i * 64 + 16, 2);
+    if (flags & KV_UTXO_F_COVENANT) {
+      set_error("kv_utxo_upsert: KV_UTXO_F_COVENANT needs kv_utxo_upsert_spk");
+      return -1;
+    }
+  }
   return utxo_upsert_nolock(ctx, outpoints, entries64, n);
 }
 
@@ -1883,15 +1896,28 @@ static int arena_reserve(kv_ctx *ctx, uint64_t need) {
   return 0;
 }
 
+/* does this ABI record's script travel in the spk blob (and live in the
+ * arena)? Long scripts, and every covenant entry: its id takes bytes 28..60 */
+static inline bool utxo_entry_needs_arena(const uint8_t *e) {
+  uint16_t flags;
+  uint32_t spk_len;
+  memcpy(&flags, e + 16, 2);
+  memcpy(&spk_len, e + 20, 4);
+  return spk_len > 36 || (flags & KV_UTXO_F_COVENANT);
+}
+
 /* the argument rules of kv_utxo_upsert_spk: no script above KV_UTXO_MAX_SPK,
- * and spk_blob holds the long ones. *long_total = their bytes. */
+ * and spk_blob holds those of the arena entries. *long_total = their bytes,
+ * *n_arena = their number. */
 static int utxo_spk_args_check(const uint8_t *entries64, size_t spk_blob_len, size_t n,
-                               uint64_t *long_total) {
+                               uint64_t *long_total, size_t *n_arena) {
   *long_total = 0;
+  *n_arena = 0;
   for (size_t i = 0; i < n; i++) {
     uint32_t spk_len;
     memcpy(&spk_len, entries64 + i * 64 + 20, 4);
-    if (spk_len > 36) {
+    if (utxo_entry_needs_arena(entries64 + i * 64)) {
+      ++*n_arena;
       if (spk_len > KV_UTXO_MAX_SPK) {
         set_error("kv_utxo_upsert_spk: spk exceeds KV_UTXO_MAX_SPK");
         return -1;
@@ -1918,30 +1944,37 @@ static int utxo_upsert_spk_nolock(kv_ctx *ctx, const uint8_t *outpoints,
     return -1;
   }
   uint64_t long_total = 0;
-  if (utxo_spk_args_check(entries64, spk_blob_len, n, &long_total)) return -1;
-  if (long_total == 0)
+  size_t n_arena = 0;
+  if (utxo_spk_args_check(entries64, spk_blob_len, n, &long_total, &n_arena)) return -1;
+  if (n_arena == 0)
     return utxo_upsert_nolock(ctx, outpoints, entries64, n, timed);
-  int rc = arena_reserve(ctx, long_total);
-  if (rc) return rc;
   uint64_t base = ctx->arena_head;
-  HIP_CHECK(hipMemcpyAsync(ctx->d_arena.as<uint8_t>() + base, spk_blob, long_total,
-                           hipMemcpyHostToDevice, ctx->stream));
-  ctx->arena_head += long_total;
-  /* rewrite the long entries: flags |= ARENA, spk[0..4) = arena offset */
+  if (long_total) { /* covenant entries with empty scripts bring no bytes */
+    int rc = arena_reserve(ctx, long_total);
+    if (rc) return rc;
+    HIP_CHECK(hipMemcpyAsync(ctx->d_arena.as<uint8_t>() + base, spk_blob, long_total,
+                             hipMemcpyHostToDevice, ctx->stream));
+    ctx->arena_head += long_total;
+  }
+  /* rewrite the arena entries: flags |= ARENA, spk[0..4) = arena offset; a
+   * covenant entry keeps its id in 28..60 */
   std::vector<uint8_t> ents(entries64, entries64 + n * 64);
   uint64_t off = base;
   for (size_t i = 0; i < n; i++) {
     uint8_t *e = ents.data() + i * 64;
     uint32_t spk_len;
     memcpy(&spk_len, e + 20, 4);
-    if (spk_len <= 36) continue;
+    if (!utxo_entry_needs_arena(e)) continue;
     uint16_t flags;
     memcpy(&flags, e + 16, 2);
     flags |= KV_UTXO_F_SPK_ARENA;
     memcpy(e + 16, &flags, 2);
     uint32_t o32 = (uint32_t)off;
     memcpy(e + 24, &o32, 4);
-    memset(e + 28, 0, 32);
+    if (flags & KV_UTXO_F_COVENANT)
+      memset(e + 60, 0, 4);
+    else
+      memset(e + 28, 0, 32);
     off += spk_len;
   }
   return utxo_upsert_nolock(ctx, outpoints, ents.data(), n, timed);
@@ -1996,7 +2029,8 @@ static int arena_gather_nolock(kv_ctx *ctx, size_t n, TakeFn take,
     uint32_t spk_len, src;
     memcpy(&spk_len, e + 20, 4);
     memcpy(&src, e + 24, 4);
-    jobs.push_back(kv::arena_gather_job{src, spk_len, dst, 0});
+    if (spk_len) /* a covenant entry's script may be empty */
+      jobs.push_back(kv::arena_gather_job{src, spk_len, dst, 0});
     memcpy(e + 24, &dst, 4); /* rewrite to the gathered-buffer offset */
     dst += spk_len;
   }
@@ -2714,7 +2748,8 @@ static int journal_apply_nolock(kv_ctx *ctx, const uint8_t *removed_ops, size_t 
   /* every -1 of the upsert that follows the remove is decided here, before
    * anything changes */
   uint64_t long_total = 0;
-  if (utxo_spk_args_check(added_entries64, spk_blob_len, n_added, &long_total))
+  size_t n_arena = 0;
+  if (utxo_spk_args_check(added_entries64, spk_blob_len, n_added, &long_total, &n_arena))
     return -1;
   if (!ops_distinct(removed_ops, n_removed, added_ops, n_added)) {
     set_error("kv_utxo_apply_diff: outpoints are not distinct across removed and added");
@@ -2915,10 +2950,20 @@ extern "C" int kv_validate_mempool(kv_ctx *ctx, const uint8_t *blob,
     if (kvh_storage_mass(tx, h_is_coinbase(tx), &storage)) {
       tx_codes_out[t] = KV_ERR_MASS_INCOMPUTABLE;
       fees_out[t] = 0;
-    } else if (tx_codes_out[t] == 0 && feerate_threshold > 0) {
+    } else if (feerate_threshold > 0 &&
+               (tx_codes_out[t] == 0 || tx_codes_out[t] == KV_ERR_COVENANT_AUTH_INPUT ||
+                tx_codes_out[t] == KV_ERR_COVENANT_GENESIS_ID)) {
+      /* the reference checks the feerate (:57) before the covenant bindings
+       * (:58), so it wins over them. A covenant failure cleared the fee, but
+       * the amount checks before it passed: the fee is the plain difference. */
+      uint64_t fee = fees_out[t];
+      if (tx_codes_out[t]) {
+        fee = 0;
+        for (const auto &in : tx.inputs) fee += in.utxo_amount;
+        for (const auto &o : tx.outputs) fee -= o.value;
+      }
       uint64_t m = kvh_normalized_mass(tx, storage);
-      if (m > 0 &&
-          (double)fees_out[t] / (double)m <= feerate_threshold) {
+      if (m > 0 && (double)fee / (double)m <= feerate_threshold) {
         tx_codes_out[t] = KV_ERR_FEERATE_TOO_LOW;
         fees_out[t] = 0;
       }
@@ -3134,9 +3179,15 @@ static int populate_blob_nolock(kv_ctx *ctx, const uint8_t *blob, size_t blob_le
       for (auto &in : tx.inputs) {
         int hit = (found[ii / 64] >> (ii % 64)) & 1;
         uint32_t spk_len = 0;
-        if (hit) memcpy(&spk_len, entries.data() + ii * 64 + 20, 4);
-        else if (!pre_codes[t]) pre_codes[t] = KV_ERR_MISSING_OUTPOINT;
-        sz += 52 + in.sig_script_len + 24 + spk_len;
+        uint16_t eflags = 0;
+        if (hit) {
+          memcpy(&spk_len, entries.data() + ii * 64 + 20, 4);
+          memcpy(&eflags, entries.data() + ii * 64 + 16, 2);
+        } else if (!pre_codes[t]) {
+          pre_codes[t] = KV_ERR_MISSING_OUTPOINT;
+        }
+        sz += 52 + in.sig_script_len + 24 + spk_len +
+              ((eflags & KV_UTXO_F_COVENANT) ? 32 : 0);
         ii++;
       }
       uint32_t outs_start = tx.outputs.empty() ? tx_end : tx.output_offs[0];
@@ -3183,7 +3234,7 @@ static int populate_blob_nolock(kv_ctx *ctx, const uint8_t *blob, size_t blob_le
       memcpy(dst, &amount, 8);
       memcpy(dst + 8, &daa, 8);
       dst[16] = (uint8_t)(eflags & 1);
-      dst[17] = 0; /* covenants out of round-1 scope */
+      dst[17] = (eflags & KV_UTXO_F_COVENANT) ? 1 : 0;
       memcpy(dst + 18, &spkv, 2);
       memcpy(dst + 20, &spk_len, 4);
       dst += 24;
@@ -3196,6 +3247,10 @@ static int populate_blob_nolock(kv_ctx *ctx, const uint8_t *blob, size_t blob_le
           memcpy(dst, e + 24, spk_len);
         }
         dst += spk_len;
+      }
+      if (eflags & KV_UTXO_F_COVENANT) { /* utxo_covenant_id follows the script */
+        memcpy(dst, e + 28, 32);
+        dst += 32;
       }
       ii++;
     }
@@ -3242,7 +3297,12 @@ static int build_block_diff(const vector<HTx> &txs, int n_txs, const int32_t *tx
       /* flags: coinbase txs never enter this path → bit0 = 0 */
       memcpy(e + 18, &o.spk_version, 2);
       memcpy(e + 20, &o.spk_len, 4);
-      if (o.spk_len <= 36)
+      if (o.has_covenant) { /* the id takes the inline field: script out of line */
+        const uint16_t f = KV_UTXO_F_COVENANT;
+        memcpy(e + 16, &f, 2);
+        memcpy(e + 28, o.cov_id, 32);
+      }
+      if (o.spk_len <= 36 && !o.has_covenant)
         memcpy(e + 24, o.spk, o.spk_len);
       else /* out-of-line: bytes go to the arena via upsert_spk */
         d.add_spk.insert(d.add_spk.end(), o.spk, o.spk + o.spk_len);

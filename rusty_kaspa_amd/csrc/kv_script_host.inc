@@ -1269,9 +1269,10 @@ static int kvs_exec_introspection(KScript &S, uint8_t op) {
       if ((rc = kvs_pop_i32(S, &ii))) return rc;
       if (ii < 0) return KV_SCRIPT_INVALID_INDEX;
       if ((size_t)ii >= tx.inputs.size()) return KV_SCRIPT_INVALID_INPUT_INDEX;
+      /* input_ctxs hold continuation outputs only (covenants.rs:124-143) */
       int64_t cnt = 0;
       for (auto &o : tx.outputs)
-        if (o.has_covenant && o.cov_auth_input == (uint16_t)ii) cnt++;
+        if (o.cov_auth_input == (uint16_t)ii && h_cov_is_continuation(tx, o)) cnt++;
       return kvs_push_num(S, cnt);
     }
     case 0xcc: { /* auth output idx */
@@ -1282,8 +1283,8 @@ static int kvs_exec_introspection(KScript &S, uint8_t op) {
       if ((size_t)ii >= tx.inputs.size()) return KV_SCRIPT_INVALID_INPUT_INDEX;
       int64_t seen = 0;
       for (size_t o = 0; o < tx.outputs.size(); o++)
-        if (tx.outputs[o].has_covenant &&
-            tx.outputs[o].cov_auth_input == (uint16_t)ii) {
+        if (tx.outputs[o].cov_auth_input == (uint16_t)ii &&
+            h_cov_is_continuation(tx, tx.outputs[o])) {
           if (seen == k) return kvs_push_num(S, (int64_t)o);
           seen++;
         }
@@ -1318,9 +1319,9 @@ static int kvs_exec_introspection(KScript &S, uint8_t op) {
             if (want_idx && seen == k) found = (int)i;
             seen++;
           }
-      } else {
+      } else { /* shared_ctxs list continuation outputs only */
         for (size_t o = 0; o < tx.outputs.size(); o++)
-          if (tx.outputs[o].has_covenant &&
+          if (h_cov_is_continuation(tx, tx.outputs[o]) &&
               !memcmp(tx.outputs[o].cov_id, id.data(), 32)) {
             if (want_idx && seen == k) found = (int)o;
             seen++;

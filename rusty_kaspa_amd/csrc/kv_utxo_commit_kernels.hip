@@ -14,9 +14,10 @@
  * hashed with keyed BLAKE2b-256("MuHashElement") and expanded by ChaCha20 to
  * 384 bytes = 48 LE limbs (crypto/muhash/src/lib.rs:148-169). The script is
  * read inline when spk_len ≤ 36 and IN PLACE from the arena when the entry
- * carries KV_UTXO_F_SPK_ARENA — no gather copy. The table stores no covenant
- * ids (covenant outputs are KV_ERR_BAD_BLOB on the table path), so none is
- * hashed. The function uses no wave intrinsics: tests/host_shim/
+ * carries KV_UTXO_F_SPK_ARENA — no gather copy. An entry with
+ * KV_UTXO_F_COVENANT appends the 32-byte covenant id held in bytes 28..60 of
+ * its value (muhash.rs:66-67); such a value always has its script in the
+ * arena. The function uses no wave intrinsics: tests/host_shim/
  * utxo_element.cpp compiles it with g++.
  *
  * Whole-table commitment (kv_utxo_commitment), per window of
@@ -83,13 +84,15 @@ __device__ inline void muhash_expand_element(const uint8_t hash[32], uint64_t *o
 }
 
 /* a packed 64B value whose script this code may read: inline scripts fit the
- * slot, arena scripts lie inside the arena's used prefix */
+ * slot, arena scripts lie inside the arena's used prefix. A covenant id takes
+ * the inline field, so KV_UTXO_F_COVENANT without the arena flag is refused. */
 __device__ inline int utxo_value_spk_ok(const uint8_t *val64, uint64_t arena_len) {
   uint16_t flags;
   uint32_t spk_len, off;
   memcpy(&flags, val64 + 16, 2);
   memcpy(&spk_len, val64 + 20, 4);
-  if (!(flags & KV_UTXO_F_SPK_ARENA)) return spk_len <= 36;
+  if (!(flags & KV_UTXO_F_SPK_ARENA))
+    return spk_len <= 36 && !(flags & KV_UTXO_F_COVENANT);
   memcpy(&off, val64 + 24, 4);
   return spk_len <= KV_UTXO_MAX_SPK && (uint64_t)off + spk_len <= arena_len;
 }
@@ -121,6 +124,7 @@ __device__ inline void utxo_entry_element(const uint8_t *op36, const uint8_t *va
   b2b_update_u16(S, spk_version);
   b2b_update_u64(S, spk_len);
   b2b_update(S, spk, spk_len);
+  if (flags & KV_UTXO_F_COVENANT) b2b_update(S, val64 + 28, 32);
   uint8_t hash[32];
   b2b_final(S, hash);
   muhash_expand_element(hash, out);

@@ -28,7 +28,8 @@ namespace kv {
 
 /* a packed 64B table value → the record kv_utxo_upsert_spk /
  * kv_utxo_import_chunk take, in place. Inline values are left as stored. An
- * arena value loses KV_UTXO_F_SPK_ARENA and has its 36-byte spk field zeroed;
+ * arena value loses KV_UTXO_F_SPK_ARENA and has its 36-byte spk field zeroed
+ * (a covenant value: bytes 24..28 only, the flag and the id in 28..60 stay);
  * its script length and arena offset are reported and 1 is returned. */
 __host__ __device__ inline int utxo_value_export(uint8_t *val64, uint32_t *spk_len,
                                                  uint32_t *arena_off) {
@@ -40,7 +41,7 @@ __host__ __device__ inline int utxo_value_export(uint8_t *val64, uint32_t *spk_l
   memcpy(arena_off, val64 + 24, 4);
   flags &= (uint16_t)~KV_UTXO_F_SPK_ARENA;
   memcpy(val64 + 16, &flags, 2);
-  memset(val64 + 24, 0, 36);
+  memset(val64 + 24, 0, (flags & KV_UTXO_F_COVENANT) ? 4 : 36);
   return 1;
 }
 

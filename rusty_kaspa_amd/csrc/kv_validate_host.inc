@@ -16,6 +16,7 @@
  *                     redeem push; redeem = OP_m (0x20‖pk32)×n OP_n 0xae
  */
 
+#include <algorithm>
 #include <cmath>
 #include <atomic>
 #include <condition_variable>
@@ -349,6 +350,82 @@ static void h_blake2b_keyed(const uint8_t *key, size_t keylen, const uint8_t *da
   h_b2b_compress(h, blk, t, 1);
 fin:
   for (int i = 0; i < 32; i++) out[i] = (uint8_t)(h[i / 8] >> (8 * (i % 8)));
+}
+
+
+/* ---- covenant bindings ⇔ CovenantsContext::from_tx
+ * (crypto/txscript/src/covenants.rs:101-163), called from
+ * check_covenant_info (tx_validation_in_utxo_context.rs:58,176).
+ *
+ * An output with a binding is a CONTINUATION when its authorizing input's
+ * entry carries the same covenant id; only those reach the script engine's
+ * contexts (input_ctxs / shared_ctxs). Every other bound output is a GENESIS
+ * output of the group (authorizing_input, covenant_id), and the group's id
+ * must equal consensus/core/src/hashing/covenant_id.rs over the authorizing
+ * input's outpoint and the group's outputs in ascending index. */
+static bool h_cov_is_continuation(const HTx &tx, const HOutput &o) {
+  if (!o.has_covenant || o.cov_auth_input >= tx.inputs.size()) return false;
+  const HInput &in = tx.inputs[o.cov_auth_input];
+  return in.utxo_has_cov && !memcmp(in.utxo_cov_id, o.cov_id, 32);
+}
+
+static const uint8_t H_KEY_COVENANT_ID[10] = {'C', 'o', 'v', 'e', 'n',
+                                              'a', 'n', 't', 'I', 'D'};
+
+static void h_put_le(vector<uint8_t> &v, uint64_t x, int bytes) {
+  for (int i = 0; i < bytes; i++) v.push_back((uint8_t)(x >> (8 * i)));
+}
+
+/* 0, KV_ERR_COVENANT_AUTH_INPUT or KV_ERR_COVENANT_GENESIS_ID. The reference
+ * walks its genesis groups in HashMap order, so which of two failures it
+ * reports is unspecified there; here an out-of-bounds authorizing input wins
+ * (the reference returns it from the first loop, before any hashing). Every
+ * failing group gives the same code, so the order the groups are hashed in
+ * (by authorizing input, then id) cannot show. Sorting keeps a transaction of
+ * many one-output groups at n log n. */
+static int kvh_check_covenant_info(const HTx &tx) {
+  vector<uint32_t> gen; /* genesis outputs */
+  for (uint32_t i = 0; i < tx.outputs.size(); i++) {
+    const HOutput &o = tx.outputs[i];
+    if (!o.has_covenant) continue;
+    if (o.cov_auth_input >= tx.inputs.size()) return KV_ERR_COVENANT_AUTH_INPUT;
+    if (!h_cov_is_continuation(tx, o)) gen.push_back(i);
+  }
+  if (gen.empty()) return 0;
+  auto group_cmp = [&](uint32_t a, uint32_t b) {
+    const HOutput &x = tx.outputs[a], &y = tx.outputs[b];
+    if (x.cov_auth_input != y.cov_auth_input)
+      return x.cov_auth_input < y.cov_auth_input ? -1 : 1;
+    return memcmp(x.cov_id, y.cov_id, 32);
+  };
+  /* ties keep ascending output index: the order the id hashes a group in */
+  std::sort(gen.begin(), gen.end(), [&](uint32_t a, uint32_t b) {
+    int c = group_cmp(a, b);
+    return c ? c < 0 : a < b;
+  });
+  vector<uint8_t> buf;
+  for (size_t lo = 0, hi; lo < gen.size(); lo = hi) {
+    for (hi = lo + 1; hi < gen.size() && group_cmp(gen[lo], gen[hi]) == 0;) hi++;
+    const HOutput &first = tx.outputs[gen[lo]];
+    const HInput &in = tx.inputs[first.cov_auth_input];
+    buf.clear();
+    buf.insert(buf.end(), in.prev_tx_id, in.prev_tx_id + 32);
+    h_put_le(buf, in.prev_index, 4);
+    h_put_le(buf, hi - lo, 8);
+    for (size_t k = lo; k < hi; k++) {
+      const HOutput &o = tx.outputs[gen[k]];
+      h_put_le(buf, gen[k], 4);
+      h_put_le(buf, o.value, 8);
+      h_put_le(buf, o.spk_version, 2);
+      h_put_le(buf, o.spk_len, 8);
+      buf.insert(buf.end(), o.spk, o.spk + o.spk_len);
+    }
+    uint8_t id[32];
+    h_blake2b_keyed(H_KEY_COVENANT_ID, sizeof H_KEY_COVENANT_ID, buf.data(), buf.size(),
+                    id);
+    if (memcmp(id, first.cov_id, 32)) return KV_ERR_COVENANT_GENESIS_ID;
+  }
+  return 0;
 }
 
 

@@ -13,6 +13,14 @@ import os
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB_PATH = os.path.join(_REPO, "rusty_kaspa_amd", "libkaspa_gpu.so")
 
+# UTXO entry flags (bytes 16..18 of a 64-byte record) and the covenant-binding
+# result codes, as in include/kaspa_engine_abi.h
+KV_UTXO_F_COINBASE = 1
+KV_UTXO_F_SPK_ARENA = 2
+KV_UTXO_F_COVENANT = 4
+KV_ERR_COVENANT_AUTH_INPUT = 13
+KV_ERR_COVENANT_GENESIS_ID = 14
+
 
 class KvParams(ctypes.Structure):
     _fields_ = [("coinbase_maturity", ctypes.c_uint64),
