@@ -39,6 +39,11 @@
  *   kv_utxo_journal_stats   what the undo journal holds
  *   kv_validate_block_utxo_undo  kv_validate_block_utxo(apply_diff = 1) with a
  *                             revertible diff
+ *   kv_utxo_balance_by_spk  ⇔ UtxoIndexApi::get_balance_by_script_public_keys
+ *                             and get_circulating_supply
+ *                             (indexes/utxoindex/src/core/api/mod.rs:23-30)
+ *   kv_utxo_find_by_spk     ⇔ UtxoIndexApi::get_utxos_by_script_public_keys
+ *                             (same place), paginated
  *
  * No torch types cross this boundary: plain pointers and sizes only.
  * See INTEGRATION.md for the Rust-side binding a maintainer would add.
@@ -444,6 +449,90 @@ int kv_utxo_export_chunk(kv_ctx *ctx, uint64_t *cursor /* in/out, slot index; st
                          uint8_t *outpoints_out /*[36*max]*/, uint8_t *entries_out /*[64*max]*/,
                          uint8_t *spk_out, size_t spk_cap, size_t *spk_used,
                          size_t *n_out);
+
+/* ---- queries by script public key: balances, supply, entries ----
+ * ⇔ the utxoindex (indexes/utxoindex/src/core/api/mod.rs:23-30), which in the
+ *   reference is a second database keyed version u16 ‖ len u64 ‖ script ‖
+ *   outpoint (indexes/utxoindex/src/stores/indexed_utxos.rs:156-198),
+ *   re-derived from every virtual diff and rebuilt by resync. Here both calls
+ *   are a filtered scan of the one GPU-resident table: there is no secondary
+ *   index to keep in step with reorgs.
+ * A query is one script public key: kv_spk_query gives its version and length
+ * (`zero` must be 0), and the scripts of all queries lie concatenated in query
+ * order in spk_blob. At most KV_UTXO_QUERY_MAX queries per call.
+ * What matches: a READY entry matches query i when its spk_version, its
+ * spk_len and its spk_len script bytes all equal the query's. Inline scripts
+ * are read from the slot, scripts of KV_UTXO_F_SPK_ARENA values (every
+ * covenant entry among them, however short its script) in place from the
+ * arena. The covenant id plays no part in matching.
+ * Both calls are read-only on the table, take the context lock and run on the
+ * context's stream, ordered after earlier mutations. The queries are hashed on
+ * the host into an open-addressing table of at least 2·n_q slots (64-bit hash
+ * over version, length and the script bytes; the full compare decides), which
+ * is uploaded with the blob: device scratch is bounded by KV_UTXO_QUERY_MAX
+ * (and the scripts handed in) and by the compiled scan window, never by table
+ * capacity.
+ * Both return -1, with nothing written to any output, for n_q >
+ * KV_UTXO_QUERY_MAX, a spk_len > KV_UTXO_MAX_SPK, a non-zero `zero` field,
+ * spk_blob_len != the sum of the lengths, or two identical queries (the
+ * reference takes a HashSet); and -3 when a READY entry the scan met has a
+ * script reference outside the arena (the reference is not followed). */
+#define KV_UTXO_QUERY_MAX 65536u
+typedef struct kv_spk_query {
+  uint32_t spk_len;
+  uint16_t spk_version;
+  uint16_t zero;
+} kv_spk_query;
+
+/* ⇔ get_balance_by_script_public_keys + get_circulating_supply
+ *   (indexes/utxoindex/src/core/api/mod.rs:23-30).
+ * balances_out[i] / counts_out[i]: sum of amount / number of the entries that
+ * match query i. total_amount_out / n_live_out: the same over ALL READY
+ * entries (the circulating supply as this table holds it, and kv_utxo_stats'
+ * n_live). Arithmetic is mod 2^64. n_q == 0 is legal (q, spk_blob and
+ * balances_out may be NULL) and gives the supply alone. A never-reset context
+ * gives zeros.
+ * One grid-stride pass over the slot array; per-query sums by 64-bit atomics,
+ * the supply by a wave reduction and one atomic per wave per counter. One
+ * stream synchronisation, one copy back of 16·n_q + 32 bytes. kernel_ms is
+ * hipEvent time over the pass (the upload of the query table is outside). */
+int kv_utxo_balance_by_spk(kv_ctx *ctx, const kv_spk_query *q, size_t n_q,
+                           const uint8_t *spk_blob, size_t spk_blob_len,
+                           uint64_t *balances_out /*[n_q]*/,
+                           uint64_t *counts_out /*[n_q], optional*/,
+                           uint64_t *total_amount_out /*optional*/,
+                           uint64_t *n_live_out /*optional*/,
+                           double *kernel_ms /*optional*/);
+
+/* ⇔ get_utxos_by_script_public_keys, paginated (the reference's own TODO at
+ *   indexes/utxoindex/src/stores/indexed_utxos.rs:158-159).
+ * 96-byte match record (⇔ CompactUtxoEntry, indexes/core/src/
+ * indexed_utxos.rs:24-29, with its outpoint and script):
+ *    0..36 outpoint | 36..40 query index u32 | 40..48 amount | 48..56 daa_score |
+ *   56..58 flags (KV_UTXO_F_COINBASE, KV_UTXO_F_COVENANT; arena bit cleared) |
+ *   58..64 zero | 64..96 covenant id, zeros without the flag
+ * Walk, in the shape of kv_utxo_export_chunk: start with *cursor = 0 and call
+ * until *cursor == stats.slots with *n_out == 0. Records come out in ascending
+ * slot order; a call may return fewer than max_entries, or none, and one that
+ * returns none has advanced the cursor unless it was at the end already. A
+ * full walk with no mutation in between yields every matching entry exactly
+ * once. max_entries above one scan window (kv_utxo_commitment_window()) is
+ * clamped to the window; max_entries == 0 is refused with -1. A never-reset
+ * context gives *n_out = 0 and leaves the cursor alone.
+ * One call enqueues every remaining window from *cursor (which may lie inside
+ * a window) in one go, with no host round trip per window: a window that
+ * starts when max_entries matches are already stored does nothing, so the
+ * windows that ran are a prefix of the walk. After the one stream
+ * synchronisation of the chain (a 32 B record comes back with it), the slot
+ * indices and records that were stored — fewer than max_entries + one window
+ * — are copied back, sorted by slot, and the first max_entries are returned;
+ * the cursor goes one past the last slot returned, or to the start of the
+ * first window that did nothing, or to the end. Device scratch: 104 B per
+ * stored match, (max_entries + one window) of them at most. */
+int kv_utxo_find_by_spk(kv_ctx *ctx, uint64_t *cursor /* in/out, slot index; start at 0 */,
+                        const kv_spk_query *q, size_t n_q, const uint8_t *spk_blob,
+                        size_t spk_blob_len, size_t max_entries,
+                        uint8_t *matches_out /*[96*max_entries]*/, size_t *n_out);
 
 /* ---- undo journal: a reorg reverts diffs on the device ----
  * ⇔ calculate_utxo_state_relatively (consensus/src/pipeline/virtual_processor/

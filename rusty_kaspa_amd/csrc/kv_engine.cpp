@@ -31,6 +31,7 @@
 #include "kv_utxo_commit_kernels.hip"
 #include "kv_utxo_rehash_kernels.hip"
 #include "kv_utxo_journal_kernels.hip"
+#include "kv_utxo_query_kernels.hip"
 #include "kv_validate_host.inc"
 #include "kv_script_host.inc"
 
@@ -236,6 +237,13 @@ struct kv_ctx {
   uint64_t next_token = 1;
   DeviceBuf d_jrn_rec;
   double last_revert_ms = 0.0; /* kernel_ms of the last kv_utxo_revert */
+  /* queries by script public key (kv_utxo_query_kernels.hip): the query table
+   * as built on the host and its device copy, the balance call's record and
+   * per-query sums, the find walk's record, slot list and match records.
+   * Bounded by KV_UTXO_QUERY_MAX, the scripts handed in and the scan window. */
+  std::vector<uint8_t> q_host;
+  DeviceBuf d_q_set, d_q_out, d_q_find;
+  bool query_combine = true; /* KV_UTXO_QUERY_COMBINE, read once in kv_create */
   /* split Schnorr verify (launch_schnorr_verify): the ladder kernel's R limbs
    * and pre-status, 121 B per signature. One split verify is in flight per
    * context at a time (ctx->mu held, every caller syncs before the next). */
@@ -296,6 +304,9 @@ extern "C" kv_ctx *kv_create(const kv_params *params) {
     unsigned long long v = strtoull(e, &end, 10);
     if (end != e && v > 0) ctx->schnorr_split_min = (size_t)v;
   }
+  /* the balance kernel sums a wave's matches first when they all pay into one
+   * query (DESIGN.md §3.5 has the measurement); 0 turns that off */
+  if (const char *e = getenv("KV_UTXO_QUERY_COMBINE")) ctx->query_combine = e[0] != '0';
   /* fill the shared fixed-base tables (idempotent: every context writes the
    * same final bytes): the two 8-bit tables on one lane, then the joint
    * 16-bit table with one lane per entry */
@@ -2636,6 +2647,224 @@ extern "C" int kv_utxo_export_chunk(kv_ctx *ctx, uint64_t *cursor, size_t max_en
   *cursor = m == count ? base + span : base + (uint64_t)idx[order[m - 1]] + 1;
   *n_out = m;
   if (spk_used) *spk_used = used;
+  return 0;
+}
+
+/* ---------------- queries by script public key (kv_utxo_query_kernels.hip) ---
+ * ⇔ UtxoIndexApi (indexes/utxoindex/src/core/api/mod.rs:23-30), served by a
+ * filtered scan of the table instead of the reference's second database
+ * (indexes/utxoindex/src/stores/indexed_utxos.rs:156-198). */
+
+/* where the parts of the query table lie in ctx->q_host and ctx->d_q_set:
+ * hash ‖ qidx ‖ heads ‖ offsets ‖ blob */
+struct QueryLayout {
+  uint32_t slots;
+  size_t n_q, off_qidx, off_q, off_off, off_blob, bytes;
+};
+
+/* Validate the queries and build their table in ctx->q_host with the device
+ * file's own spk_query_build. Returns -1 on any refusal of the contract. */
+static int query_set_build(kv_ctx *ctx, const char *who, const kv_spk_query *q,
+                           size_t n_q, const uint8_t *spk_blob, size_t spk_blob_len,
+                           QueryLayout *L) {
+  if ((n_q && !q) || (spk_blob_len && !spk_blob) ||
+      kv::spk_query_check(q, n_q, spk_blob_len)) {
+    set_error((std::string(who) + ": too many queries, a script over "
+               "KV_UTXO_MAX_SPK, a non-zero `zero` field, or a blob length that "
+               "is not the sum of the script lengths").c_str());
+    return -1;
+  }
+  L->slots = kv::spk_query_slots(n_q);
+  L->n_q = n_q;
+  L->off_qidx = (size_t)L->slots * 8;
+  L->off_q = L->off_qidx + (size_t)L->slots * 4;
+  L->off_off = L->off_q + n_q * sizeof(kv_spk_query);
+  L->off_blob = L->off_off + n_q * 4;
+  L->bytes = L->off_blob + spk_blob_len;
+  ctx->q_host.resize(L->bytes);
+  uint8_t *h = ctx->q_host.data();
+  if (n_q) memcpy(h + L->off_q, q, n_q * sizeof(kv_spk_query));
+  if (spk_blob_len) memcpy(h + L->off_blob, spk_blob, spk_blob_len);
+  if (kv::spk_query_build(q, n_q, spk_blob, (uint32_t *)(h + L->off_off),
+                          (uint64_t *)h, (uint32_t *)(h + L->off_qidx), L->slots)) {
+    set_error((std::string(who) + ": two identical queries").c_str());
+    return -1;
+  }
+  return 0;
+}
+
+/* queue the upload of the table query_set_build made; *S gets the device view.
+ * ctx->q_host stays as it is until the caller's synchronisation. */
+static int query_set_upload(kv_ctx *ctx, const QueryLayout &L, kv::spk_query_set *S) {
+  if (ctx->d_q_set.ensure(L.bytes)) return -2;
+  HIP_CHECK(hipMemcpyAsync(ctx->d_q_set.p, ctx->q_host.data(), L.bytes,
+                           hipMemcpyHostToDevice, ctx->stream));
+  const uint8_t *d = ctx->d_q_set.as<const uint8_t>();
+  S->hash = (const uint64_t *)d;
+  S->qidx = (const uint32_t *)(d + L.off_qidx);
+  S->q = (const kv_spk_query *)(d + L.off_q);
+  S->off = (const uint32_t *)(d + L.off_off);
+  S->blob = d + L.off_blob;
+  S->mask = L.slots - 1;
+  S->n_q = (uint32_t)L.n_q;
+  return 0;
+}
+
+extern "C" int kv_utxo_balance_by_spk(kv_ctx *ctx, const kv_spk_query *q, size_t n_q,
+                                      const uint8_t *spk_blob, size_t spk_blob_len,
+                                      uint64_t *balances_out, uint64_t *counts_out,
+                                      uint64_t *total_amount_out, uint64_t *n_live_out,
+                                      double *kernel_ms) {
+  KV_ENTER(ctx);
+  if (n_q && n_q <= KV_UTXO_QUERY_MAX && !balances_out) {
+    set_error("kv_utxo_balance_by_spk: null argument");
+    return -1;
+  }
+  QueryLayout L;
+  int rc = query_set_build(ctx, "kv_utxo_balance_by_spk", q, n_q, spk_blob,
+                           spk_blob_len, &L);
+  if (rc) return rc;
+  double ms = 0.0;
+  kv::query_rec h_rec = {};
+  std::vector<uint64_t> sums(2 * n_q, 0); /* balances ‖ counts */
+  if (ctx->d_utxo.p) { /* else never reset: the empty set */
+    kv::spk_query_set S;
+    rc = query_set_upload(ctx, L, &S);
+    if (rc) return rc;
+    const size_t out_bytes = 64 + 16 * n_q;
+    if (ctx->d_q_out.ensure(out_bytes)) return -2;
+    kv::query_rec *d_rec = ctx->d_q_out.as<kv::query_rec>();
+    unsigned long long *d_bal =
+        (unsigned long long *)(ctx->d_q_out.as<uint8_t>() + 64);
+    EventPair ev;
+    HIP_CHECK(ev.init());
+    HIP_CHECK(hipMemsetAsync(d_rec, 0, out_bytes, ctx->stream));
+    uint32_t blocks = (uint32_t)std::min<uint64_t>((ctx->utxo_cap + 255) / 256,
+                                                   KV_STATS_MAX_BLOCKS);
+    HIP_CHECK(hipEventRecord(ev.a, ctx->stream));
+    hipLaunchKernelGGL(kv::kv_utxo_balance_kernel, dim3(blocks), dim3(256), 0,
+                       ctx->stream, ctx->table(), ctx->utxo_cap, S,
+                       ctx->d_arena.as<const uint8_t>(), ctx->arena_head, d_bal,
+                       d_bal + n_q, ctx->query_combine ? 1 : 0, d_rec);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.b, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(&h_rec, d_rec, sizeof(h_rec), hipMemcpyDeviceToHost,
+                             ctx->stream));
+    if (n_q)
+      HIP_CHECK(hipMemcpyAsync(sums.data(), d_bal, 16 * n_q, hipMemcpyDeviceToHost,
+                               ctx->stream));
+    /* the single synchronisation of the call */
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ms = ev.ms();
+    if (h_rec.fail) {
+      set_error("kv_utxo_balance_by_spk: a table entry's script reference is out "
+                "of range");
+      return -3;
+    }
+  }
+  if (n_q) memcpy(balances_out, sums.data(), 8 * n_q);
+  if (n_q && counts_out) memcpy(counts_out, sums.data() + n_q, 8 * n_q);
+  if (total_amount_out) *total_amount_out = h_rec.total;
+  if (n_live_out) *n_live_out = h_rec.n_live;
+  if (kernel_ms) *kernel_ms = ms;
+  return 0;
+}
+
+extern "C" int kv_utxo_find_by_spk(kv_ctx *ctx, uint64_t *cursor, const kv_spk_query *q,
+                                   size_t n_q, const uint8_t *spk_blob,
+                                   size_t spk_blob_len, size_t max_entries,
+                                   uint8_t *matches_out, size_t *n_out) {
+  KV_ENTER(ctx);
+  if (!cursor || !n_out || !matches_out || max_entries == 0) {
+    set_error("kv_utxo_find_by_spk: null argument, or max_entries == 0");
+    return -1;
+  }
+  QueryLayout L;
+  int rc = query_set_build(ctx, "kv_utxo_find_by_spk", q, n_q, spk_blob, spk_blob_len,
+                           &L);
+  if (rc) return rc;
+  if (!ctx->d_utxo.p || *cursor >= ctx->utxo_cap || n_q == 0) {
+    /* nothing to scan: never reset (the cursor stays), the walk is over, or
+     * there is no query to match */
+    *n_out = 0;
+    if (ctx->d_utxo.p) *cursor = ctx->utxo_cap;
+    return 0;
+  }
+  kv::spk_query_set S;
+  rc = query_set_upload(ctx, L, &S);
+  if (rc) return rc;
+  *n_out = 0;
+  const uint32_t max_e = (uint32_t)std::min<size_t>(max_entries, KV_COMMIT_WINDOW);
+  const uint32_t out_cap = max_e + KV_COMMIT_WINDOW;
+  const size_t off_slots = 64, off_recs = off_slots + (size_t)out_cap * 8;
+  /* exactly the bound: (max_entries + one window) × 104 B */
+  const size_t need = off_recs + (size_t)out_cap * KV_QUERY_MATCH_BYTES;
+  if (ctx->d_q_find.cap < need && ctx->d_q_find.alloc(need)) return -2;
+  uint8_t *fb = ctx->d_q_find.as<uint8_t>();
+  kv::query_rec *d_rec = (kv::query_rec *)fb;
+  unsigned long long *d_slots = (unsigned long long *)(fb + off_slots);
+  uint8_t *d_recs = fb + off_recs;
+  const uint64_t start = *cursor, end = ctx->utxo_cap;
+  HIP_CHECK(hipMemsetAsync(d_rec, 0, sizeof(kv::query_rec), ctx->stream));
+  HIP_CHECK(hipMemsetAsync(&d_rec->first_skipped, 0xff, 4, ctx->stream));
+  /* window w of this walk starts at win_start(w); the first may be partial */
+  auto win_start = [&](uint64_t w) {
+    return w == 0 ? start : (start / KV_COMMIT_WINDOW + w) * (uint64_t)KV_COMMIT_WINDOW;
+  };
+  uint32_t w = 0;
+  for (uint64_t base = start; base < end; w++) {
+    const uint32_t n_slots = (uint32_t)std::min<uint64_t>(
+        KV_COMMIT_WINDOW - (base & (KV_COMMIT_WINDOW - 1)), end - base);
+    /* the stop rule's snapshot: what the windows before this one stored */
+    HIP_CHECK(hipMemcpyAsync(&d_rec->seen, &d_rec->count, 4, hipMemcpyDeviceToDevice,
+                             ctx->stream));
+    hipLaunchKernelGGL(kv::kv_utxo_find_kernel, dim3((n_slots + 255) / 256), dim3(256),
+                       0, ctx->stream, ctx->table(), base, n_slots, S,
+                       ctx->d_arena.as<const uint8_t>(), ctx->arena_head, max_e, w,
+                       out_cap, d_slots, d_recs, d_rec);
+    base += n_slots;
+  }
+  HIP_CHECK(hipGetLastError());
+  kv::query_rec h_rec;
+  HIP_CHECK(hipMemcpyAsync(&h_rec, d_rec, sizeof(h_rec), hipMemcpyDeviceToHost,
+                           ctx->stream));
+  /* the single synchronisation of the chain */
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (h_rec.fail) {
+    set_error("kv_utxo_find_by_spk: a table entry's script reference is out of range");
+    return -3;
+  }
+  if (h_rec.count >= out_cap) {
+    set_error("kv_utxo_find_by_spk: match count out of range");
+    return -2;
+  }
+  /* every window below `limit` ran and stored all of its matches */
+  const uint64_t limit =
+      h_rec.first_skipped == 0xffffffffu ? end : win_start(h_rec.first_skipped);
+  const uint32_t stored = h_rec.count;
+  if (stored == 0) {
+    *cursor = limit;
+    return 0;
+  }
+  std::vector<unsigned long long> slots(stored);
+  HIP_CHECK(hipMemcpy(slots.data(), d_slots, (size_t)stored * 8, hipMemcpyDeviceToHost));
+  /* positions are whatever the waves' atomics made them: sort by slot and take
+   * the first max_entries; the rest is found again by the next call */
+  std::vector<uint32_t> order(stored);
+  for (uint32_t i = 0; i < stored; i++) order[i] = i;
+  std::sort(order.begin(), order.end(),
+            [&](uint32_t a, uint32_t b) { return slots[a] < slots[b]; });
+  const uint32_t m = std::min(stored, max_e);
+  uint32_t hi = 0; /* one past the last buffer position among those returned */
+  for (uint32_t i = 0; i < m; i++) hi = std::max(hi, order[i] + 1);
+  std::vector<uint8_t> &recs = ctx->ent_buf;
+  recs.resize((size_t)hi * KV_QUERY_MATCH_BYTES);
+  HIP_CHECK(hipMemcpy(recs.data(), d_recs, recs.size(), hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < m; i++)
+    memcpy(matches_out + (size_t)i * KV_QUERY_MATCH_BYTES,
+           recs.data() + (size_t)order[i] * KV_QUERY_MATCH_BYTES, KV_QUERY_MATCH_BYTES);
+  *cursor = m < stored ? slots[order[m - 1]] + 1 : limit;
+  *n_out = m;
   return 0;
 }
 

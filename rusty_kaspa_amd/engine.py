@@ -20,6 +20,8 @@ KV_UTXO_F_SPK_ARENA = 2
 KV_UTXO_F_COVENANT = 4
 KV_ERR_COVENANT_AUTH_INPUT = 13
 KV_ERR_COVENANT_GENESIS_ID = 14
+KV_UTXO_QUERY_MAX = 65536
+KV_UTXO_MATCH_BYTES = 96  # one record of utxo_find_by_spk
 
 
 class KvParams(ctypes.Structure):
@@ -55,6 +57,20 @@ class KvUtxoJournalInfo(ctypes.Structure):
                 ("newest_token", ctypes.c_uint64),
                 ("device_bytes", ctypes.c_uint64),
                 ("last_revert_kernel_ms", ctypes.c_double)]
+
+
+class KvSpkQuery(ctypes.Structure):
+    _fields_ = [("spk_len", ctypes.c_uint32), ("spk_version", ctypes.c_uint16),
+                ("zero", ctypes.c_uint16)]
+
+
+def pack_spk_queries(queries):
+    """[(version, script_bytes)] -> (kv_spk_query array, blob, n) as
+    kv_utxo_balance_by_spk / kv_utxo_find_by_spk take them."""
+    heads = (KvSpkQuery * max(len(queries), 1))()
+    for i, (version, script) in enumerate(queries):
+        heads[i] = KvSpkQuery(len(script), version, 0)
+    return heads, b"".join(bytes(s) for _, s in queries), len(queries)
 
 
 def load_library() -> ctypes.CDLL:
@@ -256,6 +272,45 @@ class Engine:
         return (cur.value, ctypes.string_at(ops, 36 * n.value),
                 ctypes.string_at(ents, 64 * n.value),
                 ctypes.string_at(spk, used.value), n.value)
+
+    def utxo_balance_by_spk(self, queries):
+        """Balances by script public key and the circulating supply, from one
+        scan of the GPU-resident set (kv_utxo_balance_by_spk). `queries` is a
+        list of distinct (version, script_bytes); returns (balances, counts,
+        total, n_live, kernel_ms): per query the sum of amounts and the number
+        of matching entries, then the same over every live entry, all mod
+        2^64. An empty list gives the supply alone."""
+        heads, blob, n = pack_spk_queries(queries)
+        bal = (ctypes.c_uint64 * max(n, 1))()
+        cnt = (ctypes.c_uint64 * max(n, 1))()
+        total, n_live = ctypes.c_uint64(), ctypes.c_uint64()
+        ms = ctypes.c_double()
+        rc = self.lib.kv_utxo_balance_by_spk(
+            ctypes.c_void_p(self.ctx), heads, ctypes.c_size_t(n), blob,
+            ctypes.c_size_t(len(blob)), bal, cnt, ctypes.byref(total),
+            ctypes.byref(n_live), ctypes.byref(ms))
+        self._check(rc)
+        return list(bal[:n]), list(cnt[:n]), total.value, n_live.value, ms.value
+
+    def utxo_find_by_spk(self, cursor: int, queries, max_entries: int):
+        """One step of the walk over the entries whose script public key is
+        one of `queries` (kv_utxo_find_by_spk), from slot `cursor`: (cursor,
+        records, n), records being n 96-byte match records (outpoint 36 ‖
+        query index u32 ‖ amount u64 ‖ daa_score u64 ‖ flags u16 ‖ 6 zero
+        bytes ‖ covenant id 32) in slot order. The walk is over when the
+        returned cursor equals utxo_stats()["slots"] and n == 0."""
+        heads, blob, n = pack_spk_queries(queries)
+        cur = ctypes.c_uint64(cursor)
+        out = (ctypes.c_uint8 * (KV_UTXO_MATCH_BYTES * max(max_entries, 1)))()
+        n_out = ctypes.c_size_t()
+        rc = self.lib.kv_utxo_find_by_spk(
+            ctypes.c_void_p(self.ctx), ctypes.byref(cur), heads,
+            ctypes.c_size_t(n), blob, ctypes.c_size_t(len(blob)),
+            ctypes.c_size_t(max_entries), out, ctypes.byref(n_out))
+        self._check(rc)
+        return (cur.value,
+                ctypes.string_at(out, KV_UTXO_MATCH_BYTES * n_out.value),
+                n_out.value)
 
     def utxo_apply_diff(self, removed_ops: bytes, added_ops: bytes = b"",
                         added_entries64: bytes = b"", spk_blob: bytes = b""):
