@@ -614,6 +614,96 @@ typedef struct kv_utxo_journal_info {
 } kv_utxo_journal_info;
 int kv_utxo_journal_stats(kv_ctx *ctx, kv_utxo_journal_info *out);
 
+/* ---- per-script changes of one journaled diff ----
+ * ⇔ the UtxoChanges behind UtxosChanged notifications:
+ *   UtxoIndexChanges::update_utxo_diff (indexes/utxoindex/src/
+ *   update_container.rs:29-51), UtxosChangedNotification::
+ *   apply_utxos_changed_subscription / filter_utxo_set (indexes/core/src/
+ *   notification.rs:81-127) and supply_change -> update_circulating_supply
+ *   (indexes/utxoindex/src/index.rs:98).
+ * The removed side of a journaled diff (amount, daa score, script and covenant
+ * id of every spent entry) exists only in the device record, and a block that
+ * went through kv_validate_block_utxo_undo never showed its diff to the host:
+ * this call reads the record `token` names and the live table, and reports the
+ * entries that left and entered the set, filtered by script public key.
+ *
+ * Change index. A record with n_removed and n_added rows has
+ * cursor_end = n_removed + 2·n_added change indices:
+ *   c <  n_removed           removed row c; value and script from the record;
+ *                            reported when the row was found at apply time
+ *   c == n_removed + 2k      added row k; the value the add overwrote, from
+ *                            the record; reported when there was one
+ *   c == n_removed + 2k + 1  added row k; the value the table holds NOW, script
+ *                            inline or from the live arena; reported when the
+ *                            outpoint is still in the table, else counted in
+ *                            n_added_gone
+ * The first two kinds are entries that left the set and carry
+ * KV_UTXO_CHANGE_F_REMOVED; the third kind entered it. With
+ * KV_UTXO_CHANGES_REVERSED the labels swap and nothing else does (⇔
+ * as_reversed: what a host needs before kv_utxo_revert of that token);
+ * added_amount / removed_amount and n_added / n_removed swap with them.
+ * Any token still in the journal is legal, not only the newest: the added side
+ * of an older record reflects the table as it is now.
+ *
+ * 96-byte change record, the match record of kv_utxo_find_by_spk with the zero
+ * bytes put to use:
+ *    0..36 outpoint | 36..40 query index u32 (0xffffffff with
+ *   KV_UTXO_CHANGES_ALL) | 40..48 amount | 48..56 daa_score |
+ *   56..58 flags (KV_UTXO_F_COINBASE, KV_UTXO_F_COVENANT,
+ *   KV_UTXO_CHANGE_F_REMOVED; arena bit cleared) | 58..60 spk_version |
+ *   60..64 spk_len | 64..96 covenant id, zeros without the flag
+ * Queries are those of kv_utxo_find_by_spk, matched the same way. n_q == 0
+ * without KV_UTXO_CHANGES_ALL is legal: the totals and no record.
+ *
+ * Walk: start with *cursor = 0 and call until *cursor == res_out->cursor_end.
+ * Records come out in ascending change index; the cursor goes one past the
+ * last index returned, or to cursor_end when nothing is left. A walk with no
+ * mutation in between yields each change exactly once; with spk_out == NULL it
+ * takes at most matches / max_entries + 1 calls. The totals in res_out are
+ * over the WHOLE record, whatever the filter and the cursor.
+ * Scripts: with spk_out non-NULL the script of every returned record, of any
+ * length, is appended to it in record order (*spk_used = total). spk_cap must
+ * be >= KV_UTXO_MAX_SPK, so one entry always fits; a chunk ends early, with
+ * the cursor before the next record, when that record's script would not fit
+ * (the rule of kv_utxo_export_chunk). With spk_out == NULL, spk_cap and
+ * spk_used are ignored.
+ *
+ * One launch with a lane per change index, one synchronisation with a 48 B
+ * record back (counts, totals, status); then the stored indices are copied
+ * back and sorted, the prefix that fits is cut and its records are copied
+ * back; long scripts are gathered once per source (record blob, live arena).
+ * Device scratch: 152 B × (cursor_end - *cursor) plus the query table; never a
+ * function of table capacity. Read-only on table and journal, under the
+ * context lock, on the context's stream; kv_utxo_rehash between the apply and
+ * this call changes nothing in the answer.
+ * Returns -1, with nothing written to any output and the cursor left alone,
+ * for a null cursor, n_out, res_out or changes_out, max_entries == 0, unknown
+ * flag bits, KV_UTXO_CHANGES_ALL with n_q != 0, a token that is not in the
+ * journal (never issued, reverted, dropped, or cleared by kv_utxo_reset),
+ * *cursor > cursor_end, spk_out with spk_cap < KV_UTXO_MAX_SPK, and every
+ * refusal of the queries listed at kv_utxo_find_by_spk; -3 when a value the
+ * kernel met has a script reference out of range (it is not followed). */
+#define KV_UTXO_CHANGES_REVERSED 1u   /* report the record as its REVERT would change the set */
+#define KV_UTXO_CHANGES_ALL      2u   /* no filter (⇔ subscription.to_all()); n_q must be 0 */
+#define KV_UTXO_CHANGE_F_REMOVED 0x8000u /* in a change record's flags: the entry left the set */
+
+typedef struct kv_utxo_changes_result {
+  uint64_t cursor_end;      /* n_removed + 2*n_added of the record: the walk ends here */
+  uint64_t added_amount;    /* sum of amount over ALL entries the record adds, mod 2^64 */
+  uint64_t removed_amount;  /* same for removed; supply_change = added - removed */
+  uint64_t n_added, n_removed;   /* the entries counted in those sums */
+  uint64_t n_added_gone;    /* added-side outpoints that are no longer READY in the table */
+  double kernel_ms;         /* hipEvents over the launch(es) of this call */
+} kv_utxo_changes_result;
+
+int kv_utxo_changes_by_spk(kv_ctx *ctx, uint64_t token, uint32_t flags,
+                           uint64_t *cursor /* in/out, change index; start at 0 */,
+                           const kv_spk_query *q, size_t n_q,
+                           const uint8_t *spk_blob, size_t spk_blob_len,
+                           size_t max_entries, uint8_t *changes_out /*[96*max_entries]*/,
+                           uint8_t *spk_out /*optional*/, size_t spk_cap, size_t *spk_used,
+                           size_t *n_out, kv_utxo_changes_result *res_out /*required*/);
+
 /* Populate + validate + (optionally) apply the UTXO diff — the full virtual
  * processor step for one block (utxo_validation.rs:351-390 populate, then
  * validation, then utxo_diff.rs:224 add_transaction per accepted tx).

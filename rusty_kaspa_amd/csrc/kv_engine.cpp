@@ -32,6 +32,7 @@
 #include "kv_utxo_rehash_kernels.hip"
 #include "kv_utxo_journal_kernels.hip"
 #include "kv_utxo_query_kernels.hip"
+#include "kv_utxo_changes_kernels.hip"
 #include "kv_validate_host.inc"
 #include "kv_script_host.inc"
 
@@ -237,6 +238,10 @@ struct kv_ctx {
   uint64_t next_token = 1;
   DeviceBuf d_jrn_rec;
   double last_revert_ms = 0.0; /* kernel_ms of the last kv_utxo_revert */
+  /* per-script changes of a record (kv_utxo_changes_kernels.hip): the copy-back
+   * record, then the stored keys and staged records of one call. Bounded by
+   * the record walked, never by table capacity. */
+  DeviceBuf d_chg;
   /* queries by script public key (kv_utxo_query_kernels.hip): the query table
    * as built on the host and its device copy, the balance call's record and
    * per-query sums, the find walk's record, slot list and match records.
@@ -3118,6 +3123,215 @@ extern "C" int kv_utxo_journal_stats(kv_ctx *ctx, kv_utxo_journal_info *out) {
   }
   for (const JournalRecord &r : ctx->journal) out->device_bytes += r.device_bytes();
   out->last_revert_kernel_ms = ctx->last_revert_ms;
+  return 0;
+}
+
+/* ---------------- per-script changes of a record (kv_utxo_changes_kernels.hip)
+ * ⇔ UtxoIndexChanges::update_utxo_diff (indexes/utxoindex/src/
+ * update_container.rs:29-51) filtered as filter_utxo_set does
+ * (indexes/core/src/notification.rs:81-127), with the supply change of
+ * indexes/utxoindex/src/index.rs:98. */
+
+/* launch the block-per-script gather over `src` into ctx->d_gout (the caller
+ * sized it) for the jobs of one source; queued, not synchronised */
+static int changes_gather(kv_ctx *ctx, const uint8_t *src,
+                          const std::vector<kv::arena_gather_job> &jobs, size_t at) {
+  if (jobs.empty()) return 0;
+  kv::arena_gather_job *d_jobs = ctx->d_gjobs.as<kv::arena_gather_job>() + at;
+  HIP_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(kv::arena_gather_job),
+                           hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(kv::kv_arena_gather_kernel, dim3((uint32_t)jobs.size()), dim3(256),
+                     0, ctx->stream, src, (const kv::arena_gather_job *)d_jobs,
+                     (uint32_t)jobs.size(), ctx->d_gout.as<uint8_t>());
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int kv_utxo_changes_by_spk(kv_ctx *ctx, uint64_t token, uint32_t flags,
+                                      uint64_t *cursor, const kv_spk_query *q, size_t n_q,
+                                      const uint8_t *spk_blob, size_t spk_blob_len,
+                                      size_t max_entries, uint8_t *changes_out,
+                                      uint8_t *spk_out, size_t spk_cap, size_t *spk_used,
+                                      size_t *n_out, kv_utxo_changes_result *res_out) {
+  KV_ENTER(ctx);
+  if (!cursor || !n_out || !res_out || !changes_out || max_entries == 0) {
+    set_error("kv_utxo_changes_by_spk: null argument, or max_entries == 0");
+    return -1;
+  }
+  const bool all = flags & KV_UTXO_CHANGES_ALL;
+  if ((flags & ~(KV_UTXO_CHANGES_REVERSED | KV_UTXO_CHANGES_ALL)) || (all && n_q)) {
+    set_error("kv_utxo_changes_by_spk: unknown flag bits, or KV_UTXO_CHANGES_ALL with "
+              "queries");
+    return -1;
+  }
+  if (spk_out && spk_cap < KV_UTXO_MAX_SPK) {
+    set_error("kv_utxo_changes_by_spk: spk_cap below KV_UTXO_MAX_SPK");
+    return -1;
+  }
+  const JournalRecord *r = nullptr;
+  for (const JournalRecord &jr : ctx->journal)
+    if (jr.token == token) r = &jr;
+  if (!r) {
+    set_error("kv_utxo_changes_by_spk: no such record in the journal");
+    return -1;
+  }
+  const uint64_t total = (uint64_t)r->n_removed + 2 * (uint64_t)r->n_added;
+  const uint64_t start = *cursor;
+  if (start > total) {
+    set_error("kv_utxo_changes_by_spk: cursor past cursor_end");
+    return -1;
+  }
+  QueryLayout L;
+  int rc = query_set_build(ctx, "kv_utxo_changes_by_spk", q, n_q, spk_blob, spk_blob_len,
+                           &L);
+  if (rc) return rc;
+
+  /* Scratch: 64 B for the copy-back record, then 144 B (staged record) + 8 B
+   * (key) per lane that can store, cursor_end - *cursor of them at most and
+   * none when there is no query to match: bounded by the record, never by
+   * table capacity. The query table (query_set_upload) comes on top. The
+   * staged records come first: they are written 16 bytes at a time. */
+  const uint64_t out_cap64 = (all || n_q) ? total - start : 0;
+  const uint32_t out_cap = (uint32_t)out_cap64; /* total < 2^32: see apply_diff */
+  const size_t off_staged = 64,
+               off_keys = off_staged + (size_t)out_cap * KV_CHANGE_STAGED_BYTES;
+  const size_t need = off_keys + (size_t)out_cap * 8;
+  kv::changes_rec h_rec = {};
+  double ms = 0.0;
+  uint8_t *cb = nullptr;
+  if (total) { /* else both sides are empty: zeros, and the walk is over */
+    kv::spk_query_set S;
+    rc = query_set_upload(ctx, L, &S);
+    if (rc) return rc;
+    if (ctx->d_chg.ensure(need)) return -2;
+    cb = ctx->d_chg.as<uint8_t>();
+    kv::changes_rec *d_rec = (kv::changes_rec *)cb;
+    EventPair ev;
+    HIP_CHECK(ev.init());
+    HIP_CHECK(hipMemsetAsync(d_rec, 0, sizeof(kv::changes_rec), ctx->stream));
+    HIP_CHECK(hipEventRecord(ev.a, ctx->stream));
+    hipLaunchKernelGGL(kv::kv_utxo_changes_kernel, dim3((uint32_t)((total + 255) / 256)),
+                       dim3(256), 0, ctx->stream, ctx->table(), ctx->utxo_cap - 1,
+                       (const uint8_t *)r->keys(), (const uint8_t *)r->vals(),
+                       (const unsigned long long *)r->found(),
+                       (unsigned long long)r->n_removed, (unsigned long long)total,
+                       r->blob.as<const uint8_t>(), r->blob_bytes,
+                       ctx->d_arena.as<const uint8_t>(), ctx->arena_head, S, flags,
+                       (unsigned long long)start, out_cap,
+                       (unsigned long long *)(cb + off_keys), cb + off_staged, d_rec);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.b, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(&h_rec, d_rec, sizeof(h_rec), hipMemcpyDeviceToHost,
+                             ctx->stream));
+    /* the single synchronisation of the launch */
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ms = ev.ms();
+    if (h_rec.fail) {
+      set_error("kv_utxo_changes_by_spk: a value's script reference is out of range");
+      return -3;
+    }
+    if (h_rec.stored > out_cap) {
+      set_error("kv_utxo_changes_by_spk: stored count out of range");
+      return -2;
+    }
+  }
+
+  /* positions are whatever the waves' atomics made them: sort the keys (change
+   * index, script length above it) and cut the prefix that fits max_entries
+   * and spk_cap */
+  const uint32_t stored = h_rec.stored;
+  std::vector<unsigned long long> keys(stored);
+  if (stored)
+    HIP_CHECK(hipMemcpy(keys.data(), cb + off_keys, (size_t)stored * 8,
+                        hipMemcpyDeviceToHost));
+  const unsigned long long idx_mask = (1ULL << KV_CHANGE_KEY_LEN_SHIFT) - 1;
+  std::vector<uint32_t> order(stored);
+  for (uint32_t i = 0; i < stored; i++) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    return (keys[a] & idx_mask) < (keys[b] & idx_mask);
+  });
+  size_t m = 0, used = 0;
+  uint32_t lo = stored, hi = 0; /* the buffer positions among those returned */
+  for (; m < stored && m < max_entries; m++) {
+    const size_t len = (size_t)(keys[order[m]] >> KV_CHANGE_KEY_LEN_SHIFT);
+    if (spk_out && used + len > spk_cap) break; /* the next chunk starts here */
+    used += len;
+    lo = std::min(lo, order[m]);
+    hi = std::max(hi, order[m] + 1);
+  }
+  /* m >= 1 when anything is stored: the first script always fits */
+  std::vector<uint8_t> &staged = ctx->ent_buf;
+  std::vector<uint8_t> gathered;
+  if (m) {
+    staged.resize((size_t)(hi - lo) * KV_CHANGE_STAGED_BYTES);
+    HIP_CHECK(hipMemcpy(staged.data(),
+                        cb + off_staged + (size_t)lo * KV_CHANGE_STAGED_BYTES,
+                        staged.size(), hipMemcpyDeviceToHost));
+  }
+  auto staged_at = [&](size_t i) {
+    return staged.data() + (size_t)(order[i] - lo) * KV_CHANGE_STAGED_BYTES;
+  };
+  if (m && spk_out && used) {
+    /* out-of-line scripts: one gather per source, both into d_gout at the
+     * offsets the scripts take in spk_out */
+    std::vector<kv::arena_gather_job> from_blob, from_arena;
+    uint32_t at = 0;
+    for (size_t i = 0; i < m; i++) {
+      uint32_t w[36];
+      memcpy(w, staged_at(i), sizeof(w));
+      const uint32_t len = w[15];
+      if (len && w[24] == KV_CHANGE_SPK_BLOB)
+        from_blob.push_back(kv::arena_gather_job{w[25], len, at, 0});
+      else if (len && w[24] == KV_CHANGE_SPK_ARENA)
+        from_arena.push_back(kv::arena_gather_job{w[25], len, at, 0});
+      at += len;
+    }
+    const size_t n_jobs = from_blob.size() + from_arena.size();
+    if (n_jobs) {
+      if (ctx->d_gjobs.ensure(n_jobs * sizeof(kv::arena_gather_job)) ||
+          ctx->d_gout.ensure(used))
+        return -2;
+      EventPair ev;
+      HIP_CHECK(ev.init());
+      HIP_CHECK(hipEventRecord(ev.a, ctx->stream));
+      rc = changes_gather(ctx, r->blob.as<const uint8_t>(), from_blob, 0);
+      if (!rc)
+        rc = changes_gather(ctx, ctx->d_arena.as<const uint8_t>(), from_arena,
+                            from_blob.size());
+      if (rc) return rc;
+      HIP_CHECK(hipEventRecord(ev.b, ctx->stream));
+      gathered.resize(used);
+      HIP_CHECK(hipMemcpyAsync(gathered.data(), ctx->d_gout.p, used,
+                               hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      ms += ev.ms();
+    }
+  }
+  /* nothing can fail from here on: write the outputs */
+  size_t at = 0;
+  for (size_t i = 0; i < m; i++) {
+    const uint8_t *s = staged_at(i);
+    memcpy(changes_out + i * KV_CHANGE_BYTES, s, KV_CHANGE_BYTES);
+    if (!spk_out) continue;
+    uint32_t len, kind;
+    memcpy(&len, s + 60, 4);
+    memcpy(&kind, s + 96, 4);
+    if (len) /* inline: the value's own field, words 26.. of the staged record */
+      memcpy(spk_out + at, kind == KV_CHANGE_SPK_INLINE ? s + 104 : gathered.data() + at,
+             len);
+    at += len;
+  }
+  *cursor = m < stored ? (keys[order[m - 1]] & idx_mask) + 1 : total;
+  *n_out = m;
+  if (spk_out && spk_used) *spk_used = used;
+  const int rev = (flags & KV_UTXO_CHANGES_REVERSED) ? 1 : 0;
+  res_out->cursor_end = total;
+  res_out->added_amount = h_rec.amount[1 - rev];
+  res_out->removed_amount = h_rec.amount[rev];
+  res_out->n_added = h_rec.count[1 - rev];
+  res_out->n_removed = h_rec.count[rev];
+  res_out->n_added_gone = h_rec.n_added_gone;
+  res_out->kernel_ms = ms;
   return 0;
 }
 

@@ -22,6 +22,11 @@ KV_ERR_COVENANT_AUTH_INPUT = 13
 KV_ERR_COVENANT_GENESIS_ID = 14
 KV_UTXO_QUERY_MAX = 65536
 KV_UTXO_MATCH_BYTES = 96  # one record of utxo_find_by_spk
+KV_UTXO_MAX_SPK = 10000
+KV_UTXO_CHANGES_REVERSED = 1  # flags of utxo_changes_by_spk
+KV_UTXO_CHANGES_ALL = 2
+KV_UTXO_CHANGE_F_REMOVED = 0x8000  # in a change record's flags
+KV_UTXO_CHANGE_BYTES = 96  # one record of utxo_changes_by_spk
 
 
 class KvParams(ctypes.Structure):
@@ -57,6 +62,16 @@ class KvUtxoJournalInfo(ctypes.Structure):
                 ("newest_token", ctypes.c_uint64),
                 ("device_bytes", ctypes.c_uint64),
                 ("last_revert_kernel_ms", ctypes.c_double)]
+
+
+class KvUtxoChangesResult(ctypes.Structure):
+    _fields_ = [("cursor_end", ctypes.c_uint64),
+                ("added_amount", ctypes.c_uint64),
+                ("removed_amount", ctypes.c_uint64),
+                ("n_added", ctypes.c_uint64),
+                ("n_removed", ctypes.c_uint64),
+                ("n_added_gone", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double)]
 
 
 class KvSpkQuery(ctypes.Structure):
@@ -350,6 +365,39 @@ class Engine:
         self._check(self.lib.kv_utxo_journal_stats(ctypes.c_void_p(self.ctx),
                                                    ctypes.byref(out)))
         return {name: getattr(out, name) for name, _ in out._fields_}
+
+    def utxo_changes_by_spk(self, token: int, queries, max_entries: int,
+                            cursor: int = 0, flags: int = 0, spk_cap: int = 0):
+        """One step of the walk over the entries the journaled diff `token`
+        removed from and added to the set, filtered by script public key
+        (kv_utxo_changes_by_spk), from change index `cursor`: (records,
+        scripts, cursor, result). records are 96-byte change records (outpoint
+        36 ‖ query index u32 ‖ amount u64 ‖ daa_score u64 ‖ flags u16 ‖
+        spk_version u16 ‖ spk_len u32 ‖ covenant id 32) in ascending change
+        index, KV_UTXO_CHANGE_F_REMOVED set on those that left the set.
+        scripts is None with spk_cap == 0, else the records' scripts
+        concatenated in record order (spk_cap >= KV_UTXO_MAX_SPK). result is a
+        dict of cursor_end, added_amount, removed_amount, n_added, n_removed,
+        n_added_gone, kernel_ms, over the whole record; the walk is over when
+        the returned cursor equals result["cursor_end"]. With
+        KV_UTXO_CHANGES_ALL in flags `queries` must be empty."""
+        heads, blob, n = pack_spk_queries(queries)
+        cur = ctypes.c_uint64(cursor)
+        out = (ctypes.c_uint8 * (KV_UTXO_CHANGE_BYTES * max(max_entries, 1)))()
+        spk = (ctypes.c_uint8 * spk_cap)() if spk_cap else None
+        used, n_out = ctypes.c_size_t(), ctypes.c_size_t()
+        res = KvUtxoChangesResult()
+        rc = self.lib.kv_utxo_changes_by_spk(
+            ctypes.c_void_p(self.ctx), ctypes.c_uint64(token),
+            ctypes.c_uint32(flags), ctypes.byref(cur), heads, ctypes.c_size_t(n),
+            blob, ctypes.c_size_t(len(blob)), ctypes.c_size_t(max_entries), out,
+            spk, ctypes.c_size_t(spk_cap), ctypes.byref(used),
+            ctypes.byref(n_out), ctypes.byref(res))
+        self._check(rc)
+        return (ctypes.string_at(out, KV_UTXO_CHANGE_BYTES * n_out.value),
+                ctypes.string_at(spk, used.value) if spk_cap else None,
+                cur.value,
+                {name: getattr(res, name) for name, _ in res._fields_})
 
     def validate_block_utxo_undo(self, blob: bytes, n_txs: int, pov_daa: int,
                                  block_daa: int, flags: int = 2,
